@@ -11,7 +11,23 @@ queued before step k's host token emission, as a serving deployment would run
 consecutive batches; every step's bitstreams are complete inside the timed
 region.  --sequential times K independent encode() calls instead.
 
-Output check: after the timed region every bitstream of the batch is hashed
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times
+the K steps and prints the result line with the headline figures only.
+Everything else below (the output check against the digests, the CPU
+baselines, the roofline / decode / single-frame / container / host-resident /
+4K legs) runs only with --full, and then as before: "verified", the extra
+legs' keys and "cpu_baseline" are null / absent on a plain run.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step
+left for the caller (Pipeline.output(i), the finished bitstream of every frame
+of the batch) as .npy files: `bitstream_bytes` (float64, every frame's length),
+`bitstream_crc32` (float64, every frame's CRC-32), `sample_frames` (float64,
+the indices of a fixed seeded sample of frames, the distinct frames among
+them) and `bitstream_<i>` (float32, the bytes of sampled frame i), within
+64 MB in all.  The inputs are synthetic and seeded, so the files of two runs
+with the same arguments compare value for value.
+
+Output check (--full): after the timed region every bitstream of the batch is hashed
 and compared with tests/golden/bench_digests.json (SHA-256 of the oracle's
 bitstream for each synthetic frame, tools/make_bench_digests.py); the line
 carries "verified": true only if every frame matched.
@@ -136,7 +152,39 @@ def parse():
                     help="only the timed encode (no roofline / decode / single-frame side measurements)")
     ap.add_argument("--sequential", action="store_true",
                     help="time K separate encode() calls (no overlap between consecutive batches)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the output check against the "
+                         "digests, the CPU baselines and the roofline / decode / side legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's bitstreams as DIR/<name>.npy (at most 64 MB)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+DUMP_SAMPLE_BYTES = 10 << 20      # bitstream bytes sampled by --dump-outputs (x4 as float32: 42 MB)
+
+
+def dump_outputs(np, d, pipes, distinct, prefix=""):
+    """--dump-outputs: every frame's bitstream length and CRC-32, and the bytes of
+    a fixed seeded sample of frames (the first `distinct` among them), as .npy."""
+    import zlib
+    os.makedirs(d, exist_ok=True)
+    outs = [pipe.output(i) for pipe, _ in pipes for i in range(pipe.n)]
+    n = len(outs)
+    np.save(os.path.join(d, prefix + "bitstream_bytes.npy"), np.array([len(o) for o in outs], np.float64))
+    np.save(os.path.join(d, prefix + "bitstream_crc32.npy"), np.array([zlib.crc32(o) for o in outs], np.float64))
+    head = list(range(min(distinct, n)))
+    rest = [int(i) for i in np.random.RandomState(0x5EED).permutation(n) if i >= len(head)]
+    picked, budget = [], DUMP_SAMPLE_BYTES
+    for i in head + rest[:28]:
+        if len(outs[i]) > budget:
+            break
+        budget -= len(outs[i])
+        picked.append(i)
+        np.save(os.path.join(d, f"{prefix}bitstream_{i}.npy"), np.frombuffer(outs[i], np.uint8).astype(np.float32))
+    np.save(os.path.join(d, prefix + "sample_frames.npy"), np.array(picked, np.float64))
 
 
 def cpu_info():
@@ -1021,14 +1069,18 @@ def main():
     frames_done = n_rank * a.steps
     total_frames = int(sum(c[0] for c in gather_counts([frames_done], red_dev)))
 
-    # output check (outside the timed region): every bitstream of every pipe
-    digests = load_digests()
+    if a.dump_outputs:
+        dump_outputs(np, a.dump_outputs, pipes, D, f"rank{rank}_" if world > 1 else "")
+
+    # output check (--full, outside the timed region): every bitstream of every pipe
+    digests = load_digests() if a.full else {}
     vok = vbad = vmiss = 0
-    for pipe, _ in pipes:
-        r = verify(pipe, pipe.n, seeds, w, h, a.quality, a.method, digests)
-        vok, vbad, vmiss = vok + r[0], vbad + r[1], vmiss + r[2]
-    vc = gather_counts([vok, vbad, vmiss], red_dev)
-    vok, vbad, vmiss = (sum(c[i] for c in vc) for i in range(3))
+    if a.full:
+        for pipe, _ in pipes:
+            r = verify(pipe, pipe.n, seeds, w, h, a.quality, a.method, digests)
+            vok, vbad, vmiss = vok + r[0], vbad + r[1], vmiss + r[2]
+        vc = gather_counts([vok, vbad, vmiss], red_dev)
+        vok, vbad, vmiss = (sum(c[i] for c in vc) for i in range(3))
     bytes_out = sum(len(pipes[0][0].output(i)) for i in range(min(B, D))) if pipes else 0
 
     if rank == 0:
@@ -1051,9 +1103,11 @@ def main():
             "vs_baseline": None,
             "dtype": "int32",
             "data": "synthetic",
-            "verified": vbad == 0 and vmiss == 0 and vok > 0,
+            "full": a.full,
+            "verified": (vbad == 0 and vmiss == 0 and vok > 0) if a.full else None,
             "verification": {"frames_checked": vok + vbad + vmiss, "matched": vok, "mismatched": vbad,
-                             "no_digest": vmiss, "against": "tests/golden/bench_digests.json (oracle SHA-256)"},
+                             "no_digest": vmiss, "against": "tests/golden/bench_digests.json (oracle SHA-256)"}
+            if a.full else None,
             "config": {"workload": f"encode_frame_lossy {w}x{h} RGBA Q{a.quality} m{a.method}",
                        "frames_per_step": total_frames // max(a.steps, 1),
                        "frames_per_step_per_gpu": n_rank, "device_batch": B, "distinct_frames": D,
@@ -1077,7 +1131,7 @@ def main():
             "avg_frame_bytes": bytes_out / max(1, min(B, D)),
         }
         # the extra legs are single-GPU measurements: only the N=1 run carries them
-        extras = not a.no_extras and world == 1
+        extras = a.full and not a.no_extras and world == 1
         if extras:
             q, m = a.quality, a.method
             tags = [f"{w}x{h}/q{q}m{m}/{sd:#010x}" for sd in seeds]
@@ -1170,7 +1224,7 @@ def main():
                         "emission workers' thread CPU time (the CPU the entropy stage consumes per frame); "
                         "threads per rank = affinity CPUs / LOCAL_WORLD_SIZE, capped by OMP_NUM_THREADS"}
         line["cpu_baseline"] = None
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(imgs, w, h, a.quality, a.method, a.cpu_seconds, digests)
         if extras:
             cb = line["cpu_baseline"] or {}

@@ -2,7 +2,7 @@
 mkdir -p gpurun_out
 for r in 1 2; do for lib in "$@"; do
   echo -n "$lib: "
-  ZWEBP_LIB=$PWD/image-webp_amd/zwebp/$lib timeout -k 10 400 python -u bench.py --no-cpu-baseline 2>/dev/null | python3 -c "
+  ZWEBP_LIB=$PWD/image-webp_amd/zwebp/$lib timeout -k 10 400 python -u bench.py --full --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(round(d['value'], 1), d['verified'], 'container', round(d['container_rgba']['container_rgba_encodes_per_s'], 1),
