@@ -24,7 +24,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
-#include <limits>
 #include <memory>
 #include <thread>
 #include <vector>
@@ -33,6 +32,7 @@
 #include "zw_common.h"
 #include "zw_host_entropy.h"
 #include "zw_host_internal.h"
+#include "zw_progress.h"
 
 extern "C" {
 hipError_t zwk_rgb2yuv(hipStream_t s, const uint8_t* img, int w, int h, int bpp, int mbw, int mbh, uint8_t* Y,
@@ -428,6 +428,29 @@ extern "C" void zw_bytes_free(zw_bytes* b)
     }
 }
 
+extern "C" int zw_host_threads(void) { return host_threads(); }
+
+// Compute units of the device (256 where it does not say).
+static int device_cus(int device)
+{
+    hipDeviceProp_t prop;
+    return hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0
+               ? prop.multiProcessorCount
+               : 256;
+}
+
+// encode_frame_lossy's dimension rule (vp8.rs:3143-3148): any u16, the header
+// keeping the low 14 bits (vp8.rs:326-327; zwh::emit_frame does the same).
+// Zero is refused (the reference has no meaningful zero-MB frame).  Frames
+// wider than the batch kernels' LDS takes (zwk_encode_max_mbw(0), 1 568 MBs)
+// run the row-parallel kernels, whose LDS holds any u16 width.
+static bool encode_dims_ok(uint32_t width, uint32_t height)
+{
+    if (width == 0 || height == 0 || width > 65535 || height > 65535) return false;
+    static const int max_mbw = zwk_encode_max_mbw(1);
+    return (int)((width + 15) / 16) <= max_mbw;
+}
+
 // --------------------------------------------------------------------------
 // Batch pipeline
 //
@@ -484,13 +507,26 @@ struct FetchBuf {
     }
 };
 
+// A lane's timing events (three pairs around the timed launches of a batch)
+// and the cross-lane "statistics queued" event (zw_pipe::p1_stats).
+enum LaneEvent { EV_YUV_BEGIN, EV_YUV_END, EV_P1_BEGIN, EV_P1_END, EV_P2_BEGIN, EV_P2_END, EV_STATS_QUEUED, EV_COUNT };
+// Timing slots.  A lane: device ms of its timed launches (kms) and host ms per
+// batch (hms).  The pipe's nine (zw_pipe_kernel_times, whose order is ABI):
+// the kernel slots, then the host slots from PIPE_MS_HOST, then the emission
+// workers' CPU ms.
+enum KernelMs { KMS_RGB2YUV, KMS_ANALYSIS, KMS_PASS1, KMS_PASS2, KMS_COUNT };
+enum HostMs { HMS_FETCH, HMS_STATS, HMS_FETCH2, HMS_EMIT, HMS_COUNT };
+enum { PIPE_MS_HOST = KMS_COUNT, PIPE_MS_EMIT_CPU = KMS_COUNT + HMS_COUNT, PIPE_MS_COUNT };
+
 struct PipeLane {
     int f0 = 0, n = 0;  // frame slice
     int chunk = 0;      // frames per chunk (kernels are launched per chunk)
     hipStream_t stream = nullptr;   // kernels of the lane
-    hipStream_t stream2 = nullptr;  // packing + copies (runs beside the next chunk's kernels)
     std::vector<hipEvent_t> cev;    // per chunk: [p1 done, p2 done]
-    hipEvent_t ev[8] = {};
+    // pass 1 / 2 of chunk c: its slot in cev and in the pack counters d_ctr
+    static int pass_slot(int c, int pass) { return 2 * c + pass - 1; }
+    hipEvent_t pass_done(int c, int pass) const { return cev[pass_slot(c, pass)]; }
+    hipEvent_t ev[EV_COUNT] = {};
     unsigned long long* d_ctr = nullptr;
     uint8_t* d_rows = nullptr;  // row-parallel encode scratch (small chunks), else null
     // [0] pass-1 records (host stats replay), [1], [2] pass-2 records of the
@@ -498,14 +534,14 @@ struct PipeLane {
     // one launch, both are copied out before either is emitted)
     FetchBuf fb[3];
     Pinned<ZwStatsOut> h_stats;          // [chunk] pass-1 statistics from k_stats
-    float kms[4] = {0, 0, 0, 0};
-    double hms[4] = {0, 0, 0, 0};  // host ms: fetch1, stats, fetch2, emit
-    double emit_cpu_ms = 0;        // thread CPU ms of the emission workers per batch
+    float kms[KMS_COUNT] = {0, 0, 0, 0};
+    double hms[HMS_COUNT] = {0, 0, 0, 0};  // host ms: fetch1, stats, fetch2, emit
+    double emit_cpu_ms = 0;                // thread CPU ms of the emission workers per batch
     // Pass 2 in frame pairs (k_encode_pass2_fp: two frames a workgroup, so a
     // launch fills the CUs with two frames per CU): chunks 2k and 2k + 1 take
     // pass 2 in one launch, pass 1 and the statistics stay per chunk.
     bool pair2 = false;
-    int p2_frames = 0;  // frames of the timed pass-2 launch (kms[3] is scaled to one chunk)
+    int p2_frames = 0;  // frames of the timed pass-2 launch (kms[KMS_PASS2] is scaled to one chunk)
     bool pair1 = false;  // the same for pass 1 (k_encode_pass1_fp)
     int p1_frames = 0;
     int rc = 0;
@@ -518,24 +554,12 @@ struct PipeLane {
     // calling thread about a millisecond per 1080p frame (pinning / staging).
     std::vector<hipStream_t> ustreams;
     std::vector<hipEvent_t> uev[2], rev[2];
-    std::vector<long long> uploaded;  // per uploader: chunks issued (over all batches), under sync->mu
-    long long p1_queued = 0;
     // DMA-engine uploads (the default when the HSA agents resolve): per uploader
     // two pinned frame slots and their completion signals.  HIP's own H2D of
     // large copies runs as a blit kernel, which waits for CUs the encode
     // launches hold, so it would not overlap them.
     std::vector<uint8_t*> ustage;      // [2 * U]
     std::vector<hsa_signal_t> usig;    // [2 * U]
-    // Emission runs on its own thread, one batch behind the lane thread.
-    // `fetched` counts the chunks whose pass-2 records it has copied out
-    // (over all batches): pass 2 of the next batch may then reuse the chunk's
-    // device buffers.  fetched = LLONG_MAX once the emitter failed.
-    struct Sync {
-        std::mutex mu;
-        std::condition_variable cv;
-        long long fetched = 0;
-    };
-    std::unique_ptr<Sync> sync = std::make_unique<Sync>();
 };
 
 struct zw_pipe {
@@ -573,17 +597,19 @@ struct zw_pipe {
     std::vector<const uint8_t*> host_frames;
     int nparts = 1;  // token partitions per frame (zw_pipe_set_token_partitions)
     std::vector<PipeLane> lanes;
-    // Cross-lane order of the pass-1 launches (lane_encode, ZW_P1_ORDER): lane
-    // g's pass 1 of a batch waits for lane g - 1's statistics kernels of that
-    // batch (lane 0: of the previous batch).  Otherwise a lane's statistics,
-    // queued behind its own pass 1, wait for CUs until the other lane's whole
-    // pass-1 launch ends, and its pass 2 after them (measured: ~30 ms of idle
-    // GPU a step).  p1_stats[g]: batches whose statistics lane g has queued
-    // (its event L.ev[6] recorded after them); INT64_MAX once the lane stopped.
-    std::mutex p1_mu;
-    std::condition_variable p1_cv;
-    std::vector<long long> p1_stats;
-    float kms[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // Cross-lane order of the pass-1 launches (LaneRun, with two lanes or more
+    // and emission on): lane g's pass 1 of a batch waits for lane g - 1's
+    // statistics kernels of that batch (lane 0: of the previous batch).
+    // Otherwise a lane's statistics, queued behind its own pass 1, wait for CUs
+    // until the other lane's whole pass-1 launch ends, and its pass 2 after
+    // them (measured: ~30 ms of idle GPU a step).  p1_stats[g]: batches whose
+    // statistics lane g has queued (its event EV_STATS_QUEUED recorded after
+    // them); stopped once the lane has ended.
+    std::vector<Progress> p1_stats;
+    float kms[PIPE_MS_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // ZW_PIPE_TRACE: the lanes print their stages' times since trace_t0 (the run's start)
+    bool trace = false;
+    double trace_t0 = 0;
     // emission workspaces (chunk_emit): one per concurrent group task at most
     std::mutex ews_mu;
     std::vector<std::unique_ptr<zwh::EmitWs>> ews;
@@ -616,12 +642,11 @@ static void pipe_free(zw_pipe* p)
         if (L.d_ctr) (void)hipFree(L.d_ctr);
         if (L.d_rows) (void)hipFree(L.d_rows);
         for (FetchBuf& b : L.fb) b.release();
-        for (int i = 0; i < 8; i++)
-            if (L.ev[i]) (void)hipEventDestroy(L.ev[i]);
+        for (hipEvent_t e : L.ev)
+            if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : L.cev)
             if (e) (void)hipEventDestroy(e);
         if (L.stream) (void)hipStreamDestroy(L.stream);
-        if (L.stream2) (void)hipStreamDestroy(L.stream2);
         for (hipStream_t u : L.ustreams) (void)hipStreamDestroy(u);
         for (uint8_t* b : L.ustage) pinned_free(b);
         if (!g_dma_poisoned.load())
@@ -636,9 +661,9 @@ static void pipe_free(zw_pipe* p)
     delete p;
 }
 
-// Lanes: independent halves of the batch, each with its own kernel and copy
-// streams.  Two lanes by default once each gets at least one full launch (one
-// frame per CU): their launches overlap, so the CUs a launch's early frames
+// Lanes: independent halves of the batch, each with its own kernel stream.
+// Two lanes by default once each gets at least one full launch (one frame
+// per CU): their launches overlap, so the CUs a launch's early frames
 // free start the other lane's work instead of idling until its slowest frame
 // ends (measured, 1024 1080p frames: 3 015 -> 3 087 encodes/s; three lanes no
 // better).  ZW_PIPE_LANES overrides.
@@ -649,10 +674,7 @@ static int pipe_lanes_for(int n, int device, int mbw)
     if (e && *e) {
         g = atoi(e);
     } else {
-        hipDeviceProp_t prop;
-        const int cus = hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0
-                            ? prop.multiProcessorCount
-                            : 256;
+        const int cus = device_cus(device);
         // where the passes run in frame pairs a lane needs two chunks (two
         // frames per CU) for them: a second lane only from four chunks
         const bool fp = zwk_encode_fp(2, mbw, 2 * cus) != 0;
@@ -671,12 +693,7 @@ static int pipe_chunk_for(int lane_frames, int device)
 {
     const char* e = getenv("ZW_PIPE_CHUNK");
     int c = e ? atoi(e) : 0;
-    if (c < 1) {
-        hipDeviceProp_t prop;
-        c = hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0
-                ? prop.multiProcessorCount
-                : 256;
-    }
+    if (c < 1) c = device_cus(device);
     return c > lane_frames ? lane_frames : c;
 }
 // Row-parallel encode kernels (one wave per MB row, spread over the CUs) for
@@ -688,23 +705,7 @@ static bool pipe_rows_for(int chunk, int mbw, int mbh, int device)
     if (mbw > batch_max_mbw) return true;  // the batch shapes cannot hold the frame's rows in LDS
     const char* e = getenv("ZW_ENC_ROWS");
     if (e && *e) return atoi(e) != 0;
-    hipDeviceProp_t prop;
-    const int cus = hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0
-                        ? prop.multiProcessorCount
-                        : 256;
-    return (long long)chunk * (mbh + 1) <= 12LL * cus;  // measured: rows win up to ~48 1080p frames
-}
-
-// encode_frame_lossy's dimension rule (vp8.rs:3143-3148): any u16, the header
-// keeping the low 14 bits (vp8.rs:326-327; zwh::emit_frame does the same).
-// Zero is refused (the reference has no meaningful zero-MB frame).  Frames
-// wider than the batch kernels' LDS takes (zwk_encode_max_mbw(0), 1 568 MBs)
-// run the row-parallel kernels, whose LDS holds any u16 width.
-static bool encode_dims_ok(uint32_t width, uint32_t height)
-{
-    if (width == 0 || height == 0 || width > 65535 || height > 65535) return false;
-    static const int max_mbw = zwk_encode_max_mbw(1);
-    return (int)((width + 15) / 16) <= max_mbw;
+    return (long long)chunk * (mbh + 1) <= 12LL * device_cus(device);  // measured: rows win up to ~48 1080p frames
 }
 
 extern "C" int zw_pipe_create(zw_ctx* ctx, int n, uint32_t width, uint32_t height, int color, uint8_t quality,
@@ -773,7 +774,6 @@ extern "C" int zw_pipe_create(zw_ctx* ctx, int n, uint32_t width, uint32_t heigh
         const int nch = (L.n + L.chunk - 1) / L.chunk;
         L.cev.assign(2 * (size_t)nch, nullptr);
         ok = ok && hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking) == hipSuccess &&
-             hipStreamCreateWithFlags(&L.stream2, hipStreamNonBlocking) == hipSuccess &&
              hipMalloc(&L.d_ctr, 2 * (size_t)nch * ZW_PACK_CTR_WORDS * sizeof(unsigned long long)) == hipSuccess &&
              hipMemset(L.d_ctr, 0, 2 * (size_t)nch * ZW_PACK_CTR_WORDS * sizeof(unsigned long long)) == hipSuccess;
         if (ok && pipe_rows_for(L.chunk, p->mbw, p->mbh, ctx->device)) {
@@ -786,7 +786,7 @@ extern "C" int zw_pipe_create(zw_ctx* ctx, int n, uint32_t width, uint32_t heigh
         // pass 2 of chunks (2k, 2k + 1) in one launch where it runs in frame pairs
         L.pair2 = ok && !L.d_rows && nch >= 2 && zwk_encode_fp(2, p->mbw, 2 * L.chunk);
         L.pair1 = ok && !L.d_rows && nch >= 2 && zwk_encode_fp(1, p->mbw, 2 * L.chunk);
-        for (int i = 0; ok && i < 8; i++) ok = hipEventCreate(&L.ev[i]) == hipSuccess;
+        for (int i = 0; ok && i < EV_COUNT; i++) ok = hipEventCreate(&L.ev[i]) == hipSuccess;
         for (size_t i = 0; ok && i < L.cev.size(); i++)
             ok = hipEventCreateWithFlags(&L.cev[i], hipEventDisableTiming) == hipSuccess;
     }
@@ -896,14 +896,14 @@ static int rows_check(zw_pipe* p, PipeLane& L)
 }
 
 // ---- per-chunk stages (frames [fa, fa + na) of a lane) ----
-// Pass 1 of frames [fa, fa + na): the encode launch alone (chunk_pass1 queues
+// Pass 1 of frames [fa, fa + na): the encode launch alone (chunk_prepass queues
 // the steps before it; a paired lane launches two chunks' pass 1 at once).
 static int chunk_pass1_encode(zw_pipe* p, PipeLane& L, int fa, int na, bool timed, bool write_recon = false)
 {
     hipStream_t s = L.stream;
     const size_t F = (size_t)fa;
     if (timed) {
-        HIPOK(hipEventRecord(L.ev[2], s));
+        HIPOK(hipEventRecord(L.ev[EV_P1_BEGIN], s));
         L.p1_frames = na;
     }
     HIPOK(rows_reset(p, L, na));
@@ -912,45 +912,41 @@ static int chunk_pass1_encode(zw_pipe* p, PipeLane& L, int fa, int na, bool time
                      write_recon ? p->d_ry + F * p->ysz : nullptr, write_recon ? p->d_ru + F * p->csz : nullptr,
                      write_recon ? p->d_rv + F * p->csz : nullptr, p->ysz, p->csz, p->mbw, p->mbh, na, nullptr,
                      L.d_rows));
-    if (timed) HIPOK(hipEventRecord(L.ev[3], s));
+    if (timed) HIPOK(hipEventRecord(L.ev[EV_P1_END], s));
     return ZW_OK;
 }
 
-static int chunk_pass1(zw_pipe* p, PipeLane& L, int fa, int na, bool timed, bool write_recon = false,
-                       int parity = 0, hipEvent_t uploaded = nullptr, hipEvent_t read = nullptr, bool encode = true)
+// The steps before pass 1 of frames [fa, fa + na), rgb2yuv to segments, from
+// input buffer `parity`.  Host-source streaming: rgb2yuv waits for `uploaded`
+// (the chunk's copies) and `read` is recorded once it has read the buffer;
+// both null for frames resident on the device.
+static int chunk_prepass(zw_pipe* p, PipeLane& L, int fa, int na, bool timed, int parity, hipEvent_t uploaded,
+                         hipEvent_t read)
 {
     hipStream_t s = L.stream;
     const size_t F = (size_t)fa;
     const int n = na;
     if (uploaded) HIPOK(hipStreamWaitEvent(s, uploaded, 0));
-    if (timed) HIPOK(hipEventRecord(L.ev[0], s));
+    if (timed) HIPOK(hipEventRecord(L.ev[EV_YUV_BEGIN], s));
     const bool packed = uploaded && p->up_pack;  // (this chunk's frames arrived as RGB)
     HIPOK(zwk_rgb2yuv(s, p->img_buf(parity) + F * p->img_stride, p->w, p->h, packed ? 3 : p->bpp, p->mbw, p->mbh,
                       p->d_Y + F * p->ysz, p->d_U + F * p->csz, p->d_V + F * p->csz, p->img_stride, p->ysz, p->csz,
                       n));
     if (read) HIPOK(hipEventRecord(read, s));
-    if (timed) HIPOK(hipEventRecord(L.ev[1], s));
+    if (timed) HIPOK(hipEventRecord(L.ev[EV_YUV_END], s));
     HIPOK(zwk_analysis(s, p->d_Y + F * p->ysz, p->d_U + F * p->csz, p->d_V + F * p->csz, p->mbw, p->mbh, p->ysz,
                        p->csz, p->d_alpha + F * p->nmb, p->d_histo + F * 256, n));
     HIPOK(zwk_segments(s, p->d_histo + F * 256, p->d_tmpl, p->d_params + F, n));
-    if (!encode) return ZW_OK;
-    return chunk_pass1_encode(p, L, fa, na, timed, write_recon);
+    return ZW_OK;
 }
 
 // Pass 2 writes each MB's packed record size (EncArgs::sizes), so packing
-// its records skips k_pack_size.  ZW_PASS2_SIZES=0 restores the separate kernel.
-static bool pass2_sizes(const zw_pipe* p)
-{
-    static const bool on = []() {
-        const char* e = getenv("ZW_PASS2_SIZES");
-        return !(e && atoi(e) == 0);
-    }();
-    return on && p->d_sizes != nullptr;
-}
+// its records skips k_pack_size.
+static bool pass2_sizes(const zw_pipe* p) { return p->d_sizes != nullptr; }
 
 // Pack the chunk's MB records on the kernel stream (right after the pass that
 // produced them: the encode kernels occupy every CU, so a pack kernel queued
-// elsewhere would wait for the next chunk's pass).  slot: 2*chunk + pass-1.
+// elsewhere would wait for the next chunk's pass).  slot: PipeLane::pass_slot.
 static int chunk_pack(zw_pipe* p, PipeLane& L, int fa, int na, const ZwMbOut* d_out, int slot)
 {
     const size_t F = (size_t)fa;
@@ -1034,7 +1030,7 @@ static int chunk_pass2(zw_pipe* p, PipeLane& L, int fa, int na, bool timed)
     hipStream_t s = L.stream;
     const size_t F = (size_t)fa;
     if (timed) {
-        HIPOK(hipEventRecord(L.ev[4], s));
+        HIPOK(hipEventRecord(L.ev[EV_P2_BEGIN], s));
         L.p2_frames = na;
     }
     HIPOK(rows_reset(p, L, na));
@@ -1043,7 +1039,7 @@ static int chunk_pass2(zw_pipe* p, PipeLane& L, int fa, int na, bool timed)
                      p->d_ry + F * p->ysz, p->d_ru + F * p->csz, p->d_rv + F * p->csz, p->ysz, p->csz, p->mbw, p->mbh,
                      na, p->d_dbg ? p->d_dbg + F * p->nmb * 16 * 34 : nullptr, L.d_rows,
                      pass2_sizes(p) ? p->d_sizes + F * p->nmb : nullptr));
-    if (timed) HIPOK(hipEventRecord(L.ev[5], s));
+    if (timed) HIPOK(hipEventRecord(L.ev[EV_P2_END], s));
     return ZW_OK;
 }
 
@@ -1085,11 +1081,92 @@ static void dump_emit_input(zw_pipe* p, const uint8_t* rec, size_t bytes, size_t
     fclose(fp);
 }
 
-// cpu_ns: the workers' thread CPU time is added to it (the host budget per frame)
-static int chunk_emit(zw_pipe* p, const FetchBuf& B, int fa, int na, int par, std::atomic<long long>& cpu_ns)
+// A workspace from the pipe's pool (its buffers stay allocated and faulted in
+// across chunks and batches; the workers are new threads per chunk), handed
+// back on exit; the holder's thread CPU time meanwhile is added to `to`.
+// ws is null where none could be allocated.
+struct EmitWsLease {
+    zw_pipe* p;
+    std::atomic<long long>& to;
+    const long long c0 = thread_cpu_ns();
+    std::unique_ptr<zwh::EmitWs> ws;
+    EmitWsLease(zw_pipe* p_, std::atomic<long long>& to_) : p(p_), to(to_)
+    {
+        {
+            std::lock_guard<std::mutex> lk(p->ews_mu);
+            if (!p->ews.empty()) {
+                ws = std::move(p->ews.back());
+                p->ews.pop_back();
+            }
+        }
+        if (!ws) ws.reset(new (std::nothrow) zwh::EmitWs);
+    }
+    ~EmitWsLease()
+    {
+        if (!ws) return;
+        {
+            std::lock_guard<std::mutex> lk(p->ews_mu);
+            p->ews.push_back(std::move(ws));
+        }
+        to.fetch_add(thread_cpu_ns() - c0, std::memory_order_relaxed);
+    }
+};
+
+// One emission task: frames [i0, i0 + K) of the chunk [fa, fa + na), coded in
+// the calling thread with workspace ws.
+static int emit_task(zw_pipe* p, const FetchBuf& B, int fa, int na, int par, int i0, int K, zwh::EmitWs* ws)
 {
     const size_t F = (size_t)fa;
     const bool has_alpha = p->color == ZW_COLOR_LA8 || p->color == ZW_COLOR_RGBA8;
+    std::vector<uint8_t>* vp8 = ws->out;
+    std::vector<uint8_t>& alph = ws->alph;
+    std::vector<uint8_t>* outs[zwh::EmitWs::kMax];
+    for (int k = 0; k < K; k++) {
+        const size_t f = F + i0 + k;
+        // WebPEncoder::encode with EncoderParams::lossy (api.rs:1291-1398) wraps
+        // the VP8 frame (and for alpha inputs the ALPH chunk) in a container
+        outs[k] = p->container ? &vp8[k] : &p->bitstreams[f];
+        outs[k]->clear();
+    }
+    if (p->nparts == 1) {
+        const ZwFrameParams* Pk[zwh::EmitWs::kMax];
+        const uint8_t* rk[zwh::EmitWs::kMax];
+        bool hk[zwh::EmitWs::kMax];
+        const uint8_t(*uk[zwh::EmitWs::kMax])[8][3][11];
+        for (int k = 0; k < K; k++) {
+            const size_t hf = hidx(p, par, F + i0 + k);
+            Pk[k] = &p->h_params[hf];
+            rk[k] = B.pack + B.finfo[2 * (i0 + k)];
+            hk[k] = p->h_have_upd[hf] != 0;
+            uk[k] = (const uint8_t(*)[8][3][11])(p->h_upd.data() + hf * 4 * 8 * 3 * 11);
+        }
+        try {
+            zwh::emit_frames(outs, Pk, rk, K, p->w, p->h, hk, uk, ws);
+        } catch (const std::bad_alloc&) {  // (the worst-case decision arenas)
+            return ZW_ENOMEM;
+        }
+    } else {
+        emit_vp8(p, *outs[0], B.pack + B.finfo[2 * i0], hidx(p, par, F + i0), na);
+    }
+    if (!p->container) return ZW_OK;
+    for (int k = 0; k < K; k++) {
+        const size_t f = F + i0 + k;
+        std::vector<uint8_t>& out = p->bitstreams[f];
+        alph.clear();
+        out.clear();
+        if (has_alpha) {
+            if (const int r = zw_alph_encode(p->host_frames[f], p->img_stride, p->w, p->h, p->color, alph)) return r;
+        }
+        const zw_metadata md = {nullptr, 0, nullptr, 0, nullptr, 0};
+        zw_webp_wrap(out, outs[k]->data(), outs[k]->size(), "VP8 ", has_alpha ? &alph : nullptr, has_alpha, p->w,
+                     p->h, md);
+    }
+    return ZW_OK;
+}
+
+// cpu_ns: the workers' thread CPU time is added to it (the host budget per frame)
+static int chunk_emit(zw_pipe* p, const FetchBuf& B, int fa, int na, int par, std::atomic<long long>& cpu_ns)
+{
     if (fa == 0) dump_emit_input(p, B.pack + B.finfo[0], (size_t)B.finfo[1], hidx(p, par, 0));
     std::atomic<int> err{ZW_OK};
     // One token partition (the default): the frames go out in groups of up to
@@ -1113,101 +1190,31 @@ static int chunk_emit(zw_pipe* p, const FetchBuf& B, int fa, int na, int par, st
     static const int per_lane_env = [] { const char* e = getenv("ZW_EMIT_THREADS"); return e ? atoi(e) : 0; }();
     const int nt = per_lane_env > 0 ? per_lane_env : host_threads();
     parallel_for((na + G - 1) / G, [&](int g) {
-        const long long c0 = thread_cpu_ns();
-        // a workspace from the pipe's pool (its buffers stay allocated and faulted
-        // in across chunks and batches; the workers are new threads per chunk)
-        std::unique_ptr<zwh::EmitWs> ws;
-        {
-            std::lock_guard<std::mutex> lk(p->ews_mu);
-            if (!p->ews.empty()) {
-                ws = std::move(p->ews.back());
-                p->ews.pop_back();
-            }
-        }
-        if (!ws) ws.reset(new (std::nothrow) zwh::EmitWs);
-        if (!ws) {
-            int ok = ZW_OK;
-            err.compare_exchange_strong(ok, ZW_ENOMEM);
-            return;
-        }
-        struct Done {
-            zw_pipe* p;
-            std::unique_ptr<zwh::EmitWs>& ws;
-            std::atomic<long long>& to;
-            long long c0;
-            ~Done()
-            {
-                {
-                    std::lock_guard<std::mutex> lk(p->ews_mu);
-                    p->ews.push_back(std::move(ws));
-                }
-                to.fetch_add(thread_cpu_ns() - c0, std::memory_order_relaxed);
-            }
-        } done{p, ws, cpu_ns, c0};
-        const int i0 = g * G, K = std::min(G, na - i0);
-        std::vector<uint8_t>* vp8 = ws->out;
-        std::vector<uint8_t>& alph = ws->alph;
-        std::vector<uint8_t>* outs[zwh::EmitWs::kMax];
-        for (int k = 0; k < K; k++) {
-            const size_t f = F + i0 + k;
-            // WebPEncoder::encode with EncoderParams::lossy (api.rs:1291-1398) wraps
-            // the VP8 frame (and for alpha inputs the ALPH chunk) in a container
-            outs[k] = p->container ? &vp8[k] : &p->bitstreams[f];
-            outs[k]->clear();
-        }
-        if (p->nparts == 1) {
-            const ZwFrameParams* Pk[zwh::EmitWs::kMax];
-            const uint8_t* rk[zwh::EmitWs::kMax];
-            bool hk[zwh::EmitWs::kMax];
-            const uint8_t(*uk[zwh::EmitWs::kMax])[8][3][11];
-            for (int k = 0; k < K; k++) {
-                const size_t hf = hidx(p, par, F + i0 + k);
-                Pk[k] = &p->h_params[hf];
-                rk[k] = B.pack + B.finfo[2 * (i0 + k)];
-                hk[k] = p->h_have_upd[hf] != 0;
-                uk[k] = (const uint8_t(*)[8][3][11])(p->h_upd.data() + hf * 4 * 8 * 3 * 11);
-            }
-            try {
-                zwh::emit_frames(outs, Pk, rk, K, p->w, p->h, hk, uk, ws.get());
-            } catch (const std::bad_alloc&) {  // (the worst-case decision arenas)
-                int ok = ZW_OK;
-                err.compare_exchange_strong(ok, ZW_ENOMEM);
-                return;
-            }
-        } else {
-            emit_vp8(p, *outs[0], B.pack + B.finfo[2 * i0], hidx(p, par, F + i0), na);
-        }
-        if (!p->container) return;
-        for (int k = 0; k < K; k++) {
-            const size_t f = F + i0 + k;
-            std::vector<uint8_t>& out = p->bitstreams[f];
-            alph.clear();
-            out.clear();
-            if (has_alpha) {
-                if (const int r = zw_alph_encode(p->host_frames[f], p->img_stride, p->w, p->h, p->color, alph)) {
-                    int ok = ZW_OK;
-                    err.compare_exchange_strong(ok, r);
-                    return;
-                }
-            }
-            const zw_metadata md = {nullptr, 0, nullptr, 0, nullptr, 0};
-            zw_webp_wrap(out, outs[k]->data(), outs[k]->size(), "VP8 ", has_alpha ? &alph : nullptr, has_alpha, p->w,
-                         p->h, md);
-        }
+        EmitWsLease lease(p, cpu_ns);
+        const int i0 = g * G;
+        const int r = lease.ws ? emit_task(p, B, fa, na, par, i0, std::min(G, na - i0), lease.ws.get()) : ZW_ENOMEM;
+        int ok = ZW_OK;
+        if (r) err.compare_exchange_strong(ok, r);
     }, nt);
     return err.load();
 }
 
 static void lane_times(PipeLane& L)
 {
-    for (int i = 0; i < 4; i++) L.kms[i] = 0.f;
-    (void)hipEventElapsedTime(&L.kms[0], L.ev[0], L.ev[1]);  // rgb2yuv
-    (void)hipEventElapsedTime(&L.kms[1], L.ev[1], L.ev[2]);  // analysis + segments
-    (void)hipEventElapsedTime(&L.kms[2], L.ev[2], L.ev[3]);  // pass 1 (per chunk of frames)
-    if (L.p1_frames > 0 && L.p1_frames != L.chunk) L.kms[2] *= (float)L.chunk / (float)L.p1_frames;
-    (void)hipEventElapsedTime(&L.kms[3], L.ev[4], L.ev[5]);  // pass 2 (per chunk of frames)
-    if (L.p2_frames > 0 && L.p2_frames != L.chunk) L.kms[3] *= (float)L.chunk / (float)L.p2_frames;
+    for (float& ms : L.kms) ms = 0.f;
+    (void)hipEventElapsedTime(&L.kms[KMS_RGB2YUV], L.ev[EV_YUV_BEGIN], L.ev[EV_YUV_END]);
+    (void)hipEventElapsedTime(&L.kms[KMS_ANALYSIS], L.ev[EV_YUV_END], L.ev[EV_P1_BEGIN]);  // analysis + segments
+    (void)hipEventElapsedTime(&L.kms[KMS_PASS1], L.ev[EV_P1_BEGIN], L.ev[EV_P1_END]);      // (per chunk of frames)
+    if (L.p1_frames > 0 && L.p1_frames != L.chunk) L.kms[KMS_PASS1] *= (float)L.chunk / (float)L.p1_frames;
+    (void)hipEventElapsedTime(&L.kms[KMS_PASS2], L.ev[EV_P2_BEGIN], L.ev[EV_P2_END]);      // (per chunk of frames)
+    if (L.p2_frames > 0 && L.p2_frames != L.chunk) L.kms[KMS_PASS2] *= (float)L.chunk / (float)L.p2_frames;
 }
+
+// One launch of a pass: chunk c0 alone, or chunks c0 and c1 = c0 + 1 where the
+// pass runs in frame pairs (PipeLane::pair1 / pair2); frames [fa, fa + na).
+struct LaunchGroup {
+    int c0, c1, fa, na;
+};
 
 // Software-pipelined encode of one lane.  Per batch: pass 1 of every chunk is
 // queued up front; then per chunk the lane thread fetches the pass-1
@@ -1221,327 +1228,326 @@ static void lane_times(PipeLane& L)
 // emission of batch b.  The per-frame header state has one copy per batch
 // parity, and pass 2 of (b+1, c) is queued only once the emitter has copied
 // out the records of (b, c), whose device buffers it reuses.
-static double g_trace_t0 = 0;
-static bool g_trace = false;
-static int lane_encode(zw_pipe* p, PipeLane& L, bool emit, int nb = 1)
-{
-    const int nch = (L.n + L.chunk - 1) / L.chunk;
-    auto ca = [&](int c) { return L.f0 + c * L.chunk; };
-    auto cn = [&](int c) { return std::min(L.chunk, L.n - c * L.chunk); };
-    const bool host = p->host_src != nullptr;
-    const long long FAILED = std::numeric_limits<long long>::max();
-    int qb = 0;  // batch whose pass 1 queue_pass1 queues next
-    // cross-lane order of the pass-1 launches (zw_pipe::p1_stats)
-    static const bool p1_order_env = [] { const char* e = getenv("ZW_P1_ORDER"); return !e || atoi(e) != 0; }();
-    const int G = (int)p->lanes.size();
-    const int lane_id = (int)(&L - p->lanes.data());
-    const bool p1_order = p1_order_env && G > 1 && emit;
-    struct OrderGuard {  // a lane that stops releases the lanes waiting on it
-        zw_pipe* p;
-        int g;
-        bool on;
-        ~OrderGuard()
-        {
-            if (!on) return;
-            {
-                std::lock_guard<std::mutex> lk(p->p1_mu);
-                p->p1_stats[g] = std::numeric_limits<long long>::max();
-            }
-            p->p1_cv.notify_all();
+// Three thread roles, each a member: the lane thread (run, queue_pass1,
+// stats_and_pass2), the U uploaders of a host-source call (upload_chunks) and
+// the emission thread (emit_batch).  Built on the lane thread's stack.
+struct LaneRun {
+    zw_pipe* const p;
+    PipeLane& L;
+    const bool emit;
+    const int nb;          // batches
+    const int nch;         // chunks of the lane
+    const bool host;       // the frames come from host memory (zw_pipe_encode_host)
+    const int G, lane_id;  // lanes of the pipe, this one's index
+    const bool p1_order;   // cross-lane order of the pass-1 launches (zw_pipe::p1_stats)
+    // The hand-shakes between the threads, each counting chunks over all batches:
+    // fetched: chunks whose pass-2 records the emitter has copied out (pass 2 of
+    //   the next batch may then reuse their device buffers); stopped once it failed.
+    // uploaded[u]: chunks uploader u has issued its copies of; stopped once it failed.
+    // p1_queued: chunks whose pass 1 the lane thread has queued (the uploaders
+    //   reuse an input buffer two batches later); stopped once the lane failed
+    //   or ended early.  p1_count: its value, for the lane thread.
+    Progress fetched;
+    std::vector<Progress> uploaded;
+    Progress p1_queued;
+    long long p1_count = 0;
+    double ms[HMS_COUNT] = {0, 0, 0, 0};  // host ms summed over the batches
+    std::atomic<long long> emit_cpu{0};
+    int emit_rc = ZW_OK;
+    std::atomic<int> up_rc{ZW_OK};
+    std::vector<std::thread> up;
+    std::thread em;  // emission of one batch, one batch behind the lane thread
+
+    LaneRun(zw_pipe* p_, PipeLane& L_, bool emit_, int nb_)
+        : p(p_), L(L_), emit(emit_), nb(nb_), nch((L_.n + L_.chunk - 1) / L_.chunk), host(p_->host_src != nullptr),
+          G((int)p_->lanes.size()), lane_id((int)(&L_ - p_->lanes.data())), p1_order(G > 1 && emit_),
+          uploaded(host ? L_.ustreams.size() : 0)
+    {
+    }
+    // Every exit joins the emitter, then the uploaders, and then releases the
+    // lanes that wait on this one's statistics.
+    ~LaneRun()
+    {
+        join_emitter();
+        join_uploaders();
+        if (p1_order) p->p1_stats[lane_id].stop();
+    }
+
+    int first(int c) const { return L.f0 + c * L.chunk; }                  // first frame of chunk c
+    int count(int c) const { return std::min(L.chunk, L.n - c * L.chunk); }  // its frames
+    template <class F>
+    int for_launch_groups(bool paired, F fn) const
+    {
+        for (int c = 0; c < nch; c++) {
+            const int c1 = (paired && (c & 1) == 0 && c + 1 < nch) ? c + 1 : c;
+            if (const int r = fn(LaunchGroup{c, c1, first(c), first(c1) + count(c1) - first(c)})) return r;
+            c = c1;
         }
-    } order_guard{p, lane_id, p1_order};
-    auto p1_order_wait = [&](int b) -> int {
+        return ZW_OK;
+    }
+    int join_emitter()
+    {
+        if (em.joinable()) em.join();
+        return emit_rc;
+    }
+    void join_uploaders()
+    {
+        if (up.empty()) return;
+        if (p1_count < (long long)nb * nch) p1_queued.stop();  // a lane that stops early releases the uploaders' waits
+        for (auto& t : up) t.join();
+        up.clear();
+    }
+
+    // ---- lane thread ----
+    // Lane g's pass 1 of batch b follows lane g - 1's statistics of that batch
+    // (lane 0: the last lane's of batch b - 1).  A neighbour that has stopped is
+    // not an error: the lane goes on without the stream wait.
+    int p1_order_wait(int b)
+    {
         if (!p1_order) return ZW_OK;
         const int prev = (lane_id + G - 1) % G;
         const long long need = lane_id == 0 ? b : b + 1;
-        if (need <= 0) return ZW_OK;
-        {
-            std::unique_lock<std::mutex> lk(p->p1_mu);
-            p->p1_cv.wait(lk, [&] { return p->p1_stats[prev] >= need; });
-            if (p->p1_stats[prev] == std::numeric_limits<long long>::max()) return ZW_OK;  // (it stopped)
-        }
-        HIPOK(hipStreamWaitEvent(L.stream, p->lanes[prev].ev[6], 0));
+        if (need <= 0 || !p->p1_stats[prev].wait_for(need)) return ZW_OK;
+        HIPOK(hipStreamWaitEvent(L.stream, p->lanes[prev].ev[EV_STATS_QUEUED], 0));
         return ZW_OK;
-    };
-    auto queue_pass1 = [&]() -> int {
-        const int b = qb++;
-        for (int c = 0; c < nch; c++) {
-            // pass 1 of chunk c alone, or of chunks c and c + 1 in one launch (pair1)
-            const int c1 = (L.pair1 && (c & 1) == 0 && c + 1 < nch) ? c + 1 : c;
-            int r = ZW_OK;
-            for (int k = c; k <= c1 && !r; k++) {
-                hipEvent_t ue = nullptr, re = nullptr;
-                if (host) {  // wait until every uploader has issued its copies of this chunk
-                    std::unique_lock<std::mutex> lk(L.sync->mu);
-                    const long long need = (long long)b * nch + k + 1;
-                    L.sync->cv.wait(lk, [&] {
-                        for (long long u : L.uploaded)
-                            if (u < need) return false;
-                        return true;
-                    });
-                    for (long long u : L.uploaded)
-                        if (u == FAILED) return ZW_EDEVICE;
-                    lk.unlock();
-                    for (size_t u = 1; u < L.ustreams.size(); u++)
-                        HIPOK(hipStreamWaitEvent(L.stream, L.uev[b & 1][u * nch + k], 0));
-                    ue = L.uev[b & 1][k];
-                    re = L.rev[b & 1][k];
-                }
-                // (the pre-pass kernels; an unpaired chunk also its pass 1, after the
-                // cross-lane wait below for chunk 0)
-                const bool enc = c1 == c && !(k == 0 && p1_order);
-                r = chunk_pass1(p, L, ca(k), cn(k), k == 0, false, host ? (b & 1) : 0, ue, re, enc);
-                if (!r && c1 == c && !enc) {
-                    r = p1_order_wait(b);
-                    if (!r) r = chunk_pass1_encode(p, L, ca(k), cn(k), k == 0);
-                }
-                if (host) {
-                    {
-                        std::lock_guard<std::mutex> lk(L.sync->mu);
-                        L.p1_queued = r ? FAILED : L.p1_queued + 1;
-                    }
-                    L.sync->cv.notify_all();
-                }
-            }
-            if (!r && c == 0 && c1 != c) r = p1_order_wait(b);
-            if (!r && c1 != c) r = chunk_pass1_encode(p, L, ca(c), ca(c1) + cn(c1) - ca(c), c == 0);
-            for (int k = c; k <= c1 && !r; k++) {
-                if (p->host_stats) {
-                    r = chunk_pack(p, L, ca(k), cn(k), p->d_out1, 2 * k);
-                } else {
-                    const size_t F = (size_t)ca(k);
-                    HIPOK(zwk_stats(L.stream, p->d_out1 + F * p->nmb, p->mbw, p->mbh,
-                                    (uint8_t*)p->d_stats_tmp + zw_stats_scratch_bytes(p->nmb, (int)F),
-                                    p->d_stats + F, cn(k)));
-                }
-                if (!r) HIPOK(hipEventRecord(L.cev[2 * k], L.stream));
-            }
-            if (r) return r;
-            c = c1;
-        }
-        if (p1_order) {  // this batch's statistics are queued: the next lane's pass 1 may follow
-            HIPOK(hipEventRecord(L.ev[6], L.stream));
-            {
-                std::lock_guard<std::mutex> lk(p->p1_mu);
-                p->p1_stats[lane_id] = b + 1;
-            }
-            p->p1_cv.notify_all();
-        }
-        return ZW_OK;
-    };
-    double fetch = 0, stats = 0, fetch2 = 0, tok = 0;
-    std::atomic<long long> emit_cpu{0};
-    int emit_rc = ZW_OK;
+    }
+    // Every uploader has issued its copies of chunk k of batch b: the kernel
+    // stream waits for them (chunk_prepass waits for uploader 0's event).
+    int wait_uploaded(int b, int k)
     {
-        std::lock_guard<std::mutex> lk(L.sync->mu);
-        L.sync->fetched = 0;
-        L.uploaded.assign(host ? L.ustreams.size() : 0, 0);
-        L.p1_queued = 0;
+        for (Progress& u : uploaded)
+            if (!u.wait_for((long long)b * nch + k + 1)) return ZW_EDEVICE;
+        for (size_t u = 1; u < L.ustreams.size(); u++)
+            HIPOK(hipStreamWaitEvent(L.stream, L.uev[b & 1][u * nch + k], 0));
+        return ZW_OK;
     }
-    // host-source uploads: batch b's chunks into input buffer b & 1, each once
-    // rgb2yuv of batch b - 2 has read that buffer's chunk (the copies of batch
-    // b + 1 run while batch b's passes hold the GPU)
-    std::atomic<int> up_rc{ZW_OK};
-    std::vector<std::thread> up;
-    if (host) {
-        const int U = (int)L.ustreams.size();
-        for (int u = 0; u < U; u++)
-            up.emplace_back([&, u, U]() {  // (U by value: it goes out of scope before the threads end)
-                (void)hipSetDevice(p->ctx->device);
-                hipStream_t us = L.ustreams[u];
-                for (int b = 0; b < nb && !up_rc; b++)
-                    for (int c = 0; c < nch && !up_rc; c++) {
-                        if (b >= 2) {
-                            std::unique_lock<std::mutex> lk(L.sync->mu);
-                            const long long need = (long long)(b - 2) * nch + c + 1;
-                            L.sync->cv.wait(lk, [&] { return L.p1_queued >= need; });
-                            if (L.p1_queued == FAILED) {
-                                up_rc = ZW_EDEVICE;
-                                L.uploaded[u] = FAILED;
-                                lk.unlock();
-                                L.sync->cv.notify_all();
-                                return;
-                            }
-                        }
-                        int r = ZW_OK;
-                        uint8_t* dst = p->img_buf(b & 1) + (size_t)ca(c) * p->img_stride;
-                        if (!L.ustage.empty()) {
-                            // staged through the uploader's two pinned slots onto a DMA
-                            // engine; the chunk is complete in HBM before it is published
-                            if (b >= 2 && hipEventSynchronize(L.rev[b & 1][c]) != hipSuccess) r = ZW_EDEVICE;
-                            bool busy[2] = {false, false};
-                            int k = 0;
-                            for (int i = u; i < cn(c) && !r; i += U, k++) {
-                                const int sl = k & 1;
-                                if (busy[sl] && (r = sdma_wait(p->ctx, L.usig[2 * u + sl]))) break;
-                                const uint8_t* src = p->host_src[(size_t)b * p->n + ca(c) + i];
-                                size_t bytes = p->img_stride;
-                                if (p->up_pack) {  // RGBA -> RGB through the slot, pinned source or not
-                                    pack_rgb(L.ustage[2 * u + sl], src, (size_t)p->w * p->h);
-                                    src = L.ustage[2 * u + sl];
-                                    bytes = (size_t)p->w * p->h * 3;
-                                } else if (const void* dp = host_pinned(src, p->img_stride)) {
-                                    src = (const uint8_t*)dp;
-                                } else {  // pageable: through the slot
-                                    memcpy(L.ustage[2 * u + sl], src, p->img_stride);
-                                    src = L.ustage[2 * u + sl];
-                                }
-                                r = sdma_h2d_start(p->ctx, dst + (size_t)i * p->img_stride, src, bytes,
-                                                   L.usig[2 * u + sl]);
-                                busy[sl] = r == ZW_OK;
-                            }
-                            for (int sl = 0; sl < 2; sl++)
-                                if (busy[sl]) {
-                                    const int w = sdma_wait(p->ctx, L.usig[2 * u + sl]);
-                                    if (!r) r = w;
-                                }
-                        } else {
-                            if (b >= 2 && hipStreamWaitEvent(us, L.rev[b & 1][c], 0) != hipSuccess) r = ZW_EDEVICE;
-                            for (int i = u; i < cn(c) && !r; i += U)
-                                if (hipMemcpyAsync(dst + (size_t)i * p->img_stride,
-                                                   p->host_src[(size_t)b * p->n + ca(c) + i], p->img_stride,
-                                                   hipMemcpyHostToDevice, us) != hipSuccess)
-                                    r = ZW_EDEVICE;
-                        }
-                        if (!r && hipEventRecord(L.uev[b & 1][u * nch + c], us) != hipSuccess) r = ZW_EDEVICE;
-                        {
-                            std::lock_guard<std::mutex> lk(L.sync->mu);
-                            L.uploaded[u] = r ? FAILED : L.uploaded[u] + 1;
-                        }
-                        L.sync->cv.notify_all();
-                        if (r) up_rc = r;
-                    }
-            });
+    // The pass-1 launch of a group, after the cross-lane wait where it is the
+    // lane's first of the batch.
+    int launch_pass1(int b, const LaunchGroup& g)
+    {
+        if (g.c0 == 0)
+            if (const int r = p1_order_wait(b)) return r;
+        return chunk_pass1_encode(p, L, g.fa, g.na, g.c0 == 0);
     }
-    auto join_up = [&]() {
-        if (up.empty()) return;
-        {  // a lane that stops early releases the uploaders' waits
-            std::lock_guard<std::mutex> lk(L.sync->mu);
-            if (L.p1_queued != FAILED && L.p1_queued < (long long)nb * nch) L.p1_queued = FAILED;
-        }
-        L.sync->cv.notify_all();
-        for (auto& t : up) t.join();
-        up.clear();
-    };
-    struct UpGuard {  // every return path joins the uploader
-        decltype(join_up)& f;
-        ~UpGuard() { f(); }
-    } up_guard{join_up};
-    // emission of batch b (runs on `em`)
-    auto emitter = [&](int b) {
-        for (int c = 0; c < nch; c++) {
-            // the chunks of one pass-2 launch: copied out first (pass 2 of the
-            // next batch may then reuse their device buffers), then emitted
-            const int c1 = (L.pair2 && (c & 1) == 0 && c + 1 < nch) ? c + 1 : c;
-            const double t0 = now_ms();
-            for (int k = c; k <= c1; k++) {
-                const int r = chunk_fetch(p, L, L.fb[1 + (k & 1)], ca(k), cn(k), 2 * k + 1, L.cev[2 * k + 1]);
-                {
-                    std::lock_guard<std::mutex> lk(L.sync->mu);
-                    L.sync->fetched = r ? FAILED : L.sync->fetched + 1;
-                }
-                L.sync->cv.notify_all();
-                if (r) {
-                    emit_rc = r;
-                    return;
-                }
+    // Pre-pass of each chunk of the group, pass 1 of the group (a chunk alone
+    // right behind its pre-pass), then the statistics (or the packed records
+    // for the host's replay) of each chunk.
+    int queue_pass1_group(int b, const LaunchGroup& g)
+    {
+        const bool paired = g.c1 != g.c0;
+        int r = ZW_OK;
+        for (int k = g.c0; k <= g.c1 && !r; k++) {
+            if (host && (r = wait_uploaded(b, k))) return r;
+            r = chunk_prepass(p, L, first(k), count(k), k == 0, host ? (b & 1) : 0, host ? L.uev[b & 1][k] : nullptr,
+                              host ? L.rev[b & 1][k] : nullptr);
+            if (!r && !paired) r = launch_pass1(b, g);
+            if (host && r) p1_queued.stop();
+            if (host && !r) {
+                p1_count++;
+                p1_queued.advance();
             }
-            const double t1 = now_ms();
-            for (int k = c; k <= c1; k++)
-                if (const int re = chunk_emit(p, L.fb[1 + (k & 1)], ca(k), cn(k), b & 1, emit_cpu)) {
-                    {  // the lane thread may wait for later chunks: release it
-                        std::lock_guard<std::mutex> lk(L.sync->mu);
-                        L.sync->fetched = FAILED;
-                    }
-                    L.sync->cv.notify_all();
-                    emit_rc = re;
-                    return;
-                }
-            tok += now_ms() - t1;
-            fetch2 += t1 - t0;
-            if (g_trace)
-                fprintf(stderr, "  lane %d batch %d chunks %d-%d: p2 fetched %.1f emit done %.1f\n", L.f0, b, c, c1,
-                        t1 - g_trace_t0, now_ms() - g_trace_t0);
-            c = c1;
         }
-    };
-    std::thread em;
-    auto join_emitter = [&]() {
-        if (em.joinable()) em.join();
-        return emit_rc;
-    };
-    auto fail = [&](int r) {
-        join_emitter();
+        if (!r && paired) r = launch_pass1(b, g);
+        for (int k = g.c0; k <= g.c1 && !r; k++) {
+            if (p->host_stats) {
+                r = chunk_pack(p, L, first(k), count(k), p->d_out1, PipeLane::pass_slot(k, 1));
+            } else {
+                const size_t F = (size_t)first(k);
+                HIPOK(zwk_stats(L.stream, p->d_out1 + F * p->nmb, p->mbw, p->mbh,
+                                (uint8_t*)p->d_stats_tmp + zw_stats_scratch_bytes(p->nmb, (int)F), p->d_stats + F,
+                                count(k)));
+            }
+            if (!r) HIPOK(hipEventRecord(L.pass_done(k, 1), L.stream));
+        }
         return r;
-    };
-    int r = queue_pass1();
-    if (r) return fail(r);
-    for (int b = 0; b < nb; b++) {
-        for (int c = 0; c < nch; c++) {
-            // pass 2 of chunk c alone, or of chunks c and c + 1 in one launch (pair2)
-            const int c1 = (L.pair2 && (c & 1) == 0 && c + 1 < nch) ? c + 1 : c;
-            for (int k = c; k <= c1; k++) {
-                const double t0 = now_ms();
-                r = p->host_stats ? chunk_fetch(p, L, L.fb[0], ca(k), cn(k), 2 * k, L.cev[2 * k])
-                                  : chunk_fetch_stats(p, L, ca(k), cn(k), L.cev[2 * k]);
-                if (r) return fail(r);
-                const double t1 = now_ms();
-                if ((r = chunk_stats(p, L, ca(k), cn(k), b & 1))) return fail(r);
-                stats += now_ms() - t1;
-                fetch += t1 - t0;
-                if (g_trace)
-                    fprintf(stderr, "  lane %d batch %d chunk %d: p1 fetched %.1f stats done %.1f\n", L.f0, b, k,
-                            t1 - g_trace_t0, now_ms() - g_trace_t0);
-                if (emit && b > 0) {  // the emitter has copied out chunk k of batch b-1
-                    std::unique_lock<std::mutex> lk(L.sync->mu);
-                    const long long need = (long long)(b - 1) * nch + k + 1;
-                    L.sync->cv.wait(lk, [&] { return L.sync->fetched >= need; });
-                    if (L.sync->fetched == FAILED) {
-                        lk.unlock();
-                        const int re = join_emitter();
-                        return re ? re : ZW_EDEVICE;
-                    }
+    }
+    int queue_pass1(int b)
+    {
+        if (const int r = for_launch_groups(L.pair1, [&](const LaunchGroup& g) { return queue_pass1_group(b, g); }))
+            return r;
+        if (p1_order) {  // this batch's statistics are queued: the next lane's pass 1 may follow
+            HIPOK(hipEventRecord(L.ev[EV_STATS_QUEUED], L.stream));
+            p->p1_stats[lane_id].advance();
+        }
+        return ZW_OK;
+    }
+    // Per chunk of the group: fetch the pass-1 statistics, build the
+    // probabilities and level costs, and wait until the emitter has copied out
+    // the chunk's records of batch b - 1; then pass 2 of the group.
+    int stats_and_pass2_group(int b, const LaunchGroup& g)
+    {
+        int r;
+        for (int k = g.c0; k <= g.c1; k++) {
+            const double t0 = now_ms();
+            r = p->host_stats ? chunk_fetch(p, L, L.fb[0], first(k), count(k), PipeLane::pass_slot(k, 1),
+                                            L.pass_done(k, 1))
+                              : chunk_fetch_stats(p, L, first(k), count(k), L.pass_done(k, 1));
+            if (r) return r;
+            const double t1 = now_ms();
+            if ((r = chunk_stats(p, L, first(k), count(k), b & 1))) return r;
+            ms[HMS_STATS] += now_ms() - t1;
+            ms[HMS_FETCH] += t1 - t0;
+            if (p->trace)
+                fprintf(stderr, "  lane %d batch %d chunk %d: p1 fetched %.1f stats done %.1f\n", L.f0, b, k,
+                        t1 - p->trace_t0, now_ms() - p->trace_t0);
+            if (emit && b > 0 && !fetched.wait_for((long long)(b - 1) * nch + k + 1)) {
+                const int re = join_emitter();  // (it failed: its code, if it has one)
+                return re ? re : ZW_EDEVICE;
+            }
+        }
+        r = chunk_pass2(p, L, g.fa, g.na, g.c0 == 0);
+        for (int k = g.c0; k <= g.c1 && !r; k++) {
+            if (emit) r = chunk_pack(p, L, first(k), count(k), p->d_out2, PipeLane::pass_slot(k, 2));
+            if (!r && hipEventRecord(L.pass_done(k, 2), L.stream) != hipSuccess) r = ZW_EDEVICE;
+        }
+        return r;
+    }
+    int stats_and_pass2(int b)
+    {
+        return for_launch_groups(L.pair2, [&](const LaunchGroup& g) { return stats_and_pass2_group(b, g); });
+    }
+    int run()
+    {
+        // host-source uploads: batch b's chunks into input buffer b & 1, each once
+        // rgb2yuv of batch b - 2 has read that buffer's chunk (the copies of batch
+        // b + 1 run while batch b's passes hold the GPU)
+        for (int u = 0; u < (int)uploaded.size(); u++) up.emplace_back([this, u] { upload_chunks(u); });
+        int r = queue_pass1(0);
+        for (int b = 0; b < nb && !r; b++) {
+            r = stats_and_pass2(b);
+            if (!r && b + 1 < nb) r = queue_pass1(b + 1);
+            if (!r && emit && !(r = join_emitter())) em = std::thread([this, b] { emit_thread(b); });
+        }
+        if (r) return r;
+        if ((r = join_emitter())) return r;
+        join_uploaders();
+        if (up_rc.load()) return up_rc.load();
+        p->out_par = (nb - 1) & 1;
+        HIPOK(hipStreamSynchronize(L.stream));
+        if ((r = rows_check(p, L))) return r;
+        for (int i = 0; i < HMS_COUNT; i++) L.hms[i] = ms[i] / nb;
+        L.emit_cpu_ms = 1e-6 * (double)emit_cpu.load() / nb;
+        lane_times(L);
+        return ZW_OK;
+    }
+
+    // ---- uploader thread u (frames i % U == u of every chunk) ----
+    // Staged through the uploader's two pinned slots onto a DMA engine; the
+    // chunk is complete in HBM before it is published.
+    int upload_chunk_dma(int u, int b, int c)
+    {
+        const int U = (int)L.ustreams.size();
+        uint8_t* dst = p->img_buf(b & 1) + (size_t)first(c) * p->img_stride;
+        int r = ZW_OK;
+        if (b >= 2 && hipEventSynchronize(L.rev[b & 1][c]) != hipSuccess) r = ZW_EDEVICE;
+        bool busy[2] = {false, false};
+        int k = 0;
+        for (int i = u; i < count(c) && !r; i += U, k++) {
+            const int sl = k & 1;
+            if (busy[sl] && (r = sdma_wait(p->ctx, L.usig[2 * u + sl]))) break;
+            const uint8_t* src = p->host_src[(size_t)b * p->n + first(c) + i];
+            size_t bytes = p->img_stride;
+            if (p->up_pack) {  // RGBA -> RGB through the slot, pinned source or not
+                pack_rgb(L.ustage[2 * u + sl], src, (size_t)p->w * p->h);
+                src = L.ustage[2 * u + sl];
+                bytes = (size_t)p->w * p->h * 3;
+            } else if (const void* dp = host_pinned(src, p->img_stride)) {
+                src = (const uint8_t*)dp;
+            } else {  // pageable: through the slot
+                memcpy(L.ustage[2 * u + sl], src, p->img_stride);
+                src = L.ustage[2 * u + sl];
+            }
+            r = sdma_h2d_start(p->ctx, dst + (size_t)i * p->img_stride, src, bytes, L.usig[2 * u + sl]);
+            busy[sl] = r == ZW_OK;
+        }
+        for (int sl = 0; sl < 2; sl++)
+            if (busy[sl]) {
+                const int w = sdma_wait(p->ctx, L.usig[2 * u + sl]);
+                if (!r) r = w;
+            }
+        return r;
+    }
+    int upload_chunk_hip(int u, int b, int c)
+    {
+        const int U = (int)L.ustreams.size();
+        hipStream_t us = L.ustreams[u];
+        uint8_t* dst = p->img_buf(b & 1) + (size_t)first(c) * p->img_stride;
+        if (b >= 2 && hipStreamWaitEvent(us, L.rev[b & 1][c], 0) != hipSuccess) return ZW_EDEVICE;
+        for (int i = u; i < count(c); i += U)
+            if (hipMemcpyAsync(dst + (size_t)i * p->img_stride, p->host_src[(size_t)b * p->n + first(c) + i],
+                               p->img_stride, hipMemcpyHostToDevice, us) != hipSuccess)
+                return ZW_EDEVICE;
+        return ZW_OK;
+    }
+    void upload_chunks(int u)
+    {
+        (void)hipSetDevice(p->ctx->device);
+        for (int b = 0; b < nb && !up_rc; b++)
+            for (int c = 0; c < nch && !up_rc; c++) {
+                // (the chunk's input buffer is free once the pre-pass of batch b - 2 is queued
+                // and, waited for below, has run; a lane that has stopped stops its uploaders)
+                if (b >= 2 && !p1_queued.wait_for((long long)(b - 2) * nch + c + 1)) {
+                    up_rc = ZW_EDEVICE;
+                    uploaded[u].stop();
+                    return;
+                }
+                int r = L.ustage.empty() ? upload_chunk_hip(u, b, c) : upload_chunk_dma(u, b, c);
+                if (!r && hipEventRecord(L.uev[b & 1][u * nch + c], L.ustreams[u]) != hipSuccess) r = ZW_EDEVICE;
+                if (r) {
+                    uploaded[u].stop();
+                    up_rc = r;
+                } else {
+                    uploaded[u].advance();
                 }
             }
-            r = chunk_pass2(p, L, ca(c), ca(c1) + cn(c1) - ca(c), c == 0);
-            for (int k = c; k <= c1 && !r; k++) {
-                if (emit) r = chunk_pack(p, L, ca(k), cn(k), p->d_out2, 2 * k + 1);
-                if (!r && hipEventRecord(L.cev[2 * k + 1], L.stream) != hipSuccess) r = ZW_EDEVICE;
-            }
-            if (r) return fail(r);
-            c = c1;
-        }
-        if (b + 1 < nb && (r = queue_pass1())) return fail(r);
-        if (emit) {
-            if ((r = join_emitter())) return r;
-            em = std::thread([&, b]() {
-                (void)hipSetDevice(p->ctx->device);
-                // Emission is throughput work beside the lanes' latency-critical
-                // steps (the statistics that release pass 2, the queueing): its
-                // thread and the workers it spawns (they inherit the nice value)
-                // yield the CPU to them.  Measured: the statistics of a chunk took
-                // up to 45 ms instead of ~2 behind two lanes' emission workers,
-                // with the GPU idle meanwhile.
-                static const int nice_em = [] { const char* e = getenv("ZW_EMIT_NICE"); return e ? atoi(e) : 5; }();
-                if (nice_em > 0) (void)setpriority(PRIO_PROCESS, (id_t)syscall(SYS_gettid), nice_em);
-                emitter(b);
-            });
-        }
     }
-    if ((r = join_emitter())) return r;
-    join_up();
-    if (up_rc.load()) return up_rc.load();
-    p->out_par = (nb - 1) & 1;
-    HIPOK(hipStreamSynchronize(L.stream));
-    if ((r = rows_check(p, L))) return r;
-    L.hms[0] = fetch / nb;
-    L.hms[1] = stats / nb;
-    L.hms[2] = fetch2 / nb;
-    L.hms[3] = tok / nb;
-    L.emit_cpu_ms = 1e-6 * (double)emit_cpu.load() / nb;
-    lane_times(L);
-    return ZW_OK;
-}
+
+    // ---- emission thread ----
+    // The chunks of one pass-2 launch: copied out first (pass 2 of the next
+    // batch may then reuse their device buffers), then emitted.  A failure
+    // stops `fetched`: the lane thread may wait for later chunks.
+    int emit_group(int b, const LaunchGroup& g)
+    {
+        const double t0 = now_ms();
+        for (int k = g.c0; k <= g.c1; k++) {
+            const int r = chunk_fetch(p, L, L.fb[1 + (k & 1)], first(k), count(k), PipeLane::pass_slot(k, 2),
+                                      L.pass_done(k, 2));
+            if (r) {
+                fetched.stop();
+                return emit_rc = r;
+            }
+            fetched.advance();
+        }
+        const double t1 = now_ms();
+        for (int k = g.c0; k <= g.c1; k++)
+            if (const int re = chunk_emit(p, L.fb[1 + (k & 1)], first(k), count(k), b & 1, emit_cpu)) {
+                fetched.stop();
+                return emit_rc = re;
+            }
+        ms[HMS_EMIT] += now_ms() - t1;
+        ms[HMS_FETCH2] += t1 - t0;
+        if (p->trace)
+            fprintf(stderr, "  lane %d batch %d chunks %d-%d: p2 fetched %.1f emit done %.1f\n", L.f0, b, g.c0, g.c1,
+                    t1 - p->trace_t0, now_ms() - p->trace_t0);
+        return ZW_OK;
+    }
+    void emit_batch(int b)
+    {
+        (void)for_launch_groups(L.pair2, [&](const LaunchGroup& g) { return emit_group(b, g); });
+    }
+    void emit_thread(int b)
+    {
+        (void)hipSetDevice(p->ctx->device);
+        // Emission is throughput work beside the lanes' latency-critical
+        // steps (the statistics that release pass 2, the queueing): its
+        // thread and the workers it spawns (they inherit the nice value)
+        // yield the CPU to them at niceness 5.  Measured: the statistics of
+        // a chunk took up to 45 ms instead of ~2 behind two lanes' emission
+        // workers, with the GPU idle meanwhile.
+        (void)setpriority(PRIO_PROCESS, (id_t)syscall(SYS_gettid), 5);
+        emit_batch(b);
+    }
+};
 
 // Run fn(lane) for every lane concurrently; returns the first error.
 template <class F>
@@ -1564,14 +1570,13 @@ static int run_lanes(zw_pipe* p, F fn)
 static void pipe_collect_times(zw_pipe* p)
 {
     // per-kernel: mean over lanes of each lane's launch duration; host: max over lanes
-    // ms[8]: the emission workers' CPU ms per batch, summed over lanes
-    for (int i = 0; i < 9; i++) p->kms[i] = 0.f;
+    // PIPE_MS_EMIT_CPU: the emission workers' CPU ms per batch, summed over lanes
+    for (float& ms : p->kms) ms = 0.f;
     for (PipeLane& L : p->lanes) {
-        for (int i = 0; i < 4; i++) {
-            p->kms[i] += L.kms[i] / (float)p->lanes.size();
-            p->kms[4 + i] = std::max(p->kms[4 + i], (float)L.hms[i]);
-        }
-        p->kms[8] += (float)L.emit_cpu_ms;
+        for (int i = 0; i < KMS_COUNT; i++) p->kms[i] += L.kms[i] / (float)p->lanes.size();
+        for (int i = 0; i < HMS_COUNT; i++)
+            p->kms[PIPE_MS_HOST + i] = std::max(p->kms[PIPE_MS_HOST + i], (float)L.hms[i]);
+        p->kms[PIPE_MS_EMIT_CPU] += (float)L.emit_cpu_ms;
     }
 }
 
@@ -1582,7 +1587,9 @@ extern "C" int zw_pipe_run_pass1(zw_pipe* p, int write_recon)
     HIPOK(hipSetDevice(p->ctx->device));
     const int r = run_lanes(p, [&](PipeLane& L) -> int {
         for (int fa = L.f0; fa < L.f0 + L.n; fa += L.chunk) {
-            int r = chunk_pass1(p, L, fa, std::min(L.chunk, L.f0 + L.n - fa), false, write_recon != 0);
+            const int na = std::min(L.chunk, L.f0 + L.n - fa);
+            int r = chunk_prepass(p, L, fa, na, false, 0, nullptr, nullptr);
+            if (!r) r = chunk_pass1_encode(p, L, fa, na, false, write_recon != 0);
             if (r) return r;
         }
         HIPOK(hipStreamSynchronize(L.stream));
@@ -1597,7 +1604,7 @@ extern "C" int zw_pipe_run_device(zw_pipe* p)
     if (!p) return ZW_EINVAL;
     if (p->broken) return ZW_EDEVICE;
     HIPOK(hipSetDevice(p->ctx->device));
-    int r = run_lanes(p, [&](PipeLane& L) -> int { return lane_encode(p, L, false); });
+    int r = run_lanes(p, [&](PipeLane& L) -> int { return LaneRun(p, L, false, 1).run(); });
     pipe_collect_times(p);
     if (r) p->broken = true;
     return r;
@@ -1609,17 +1616,17 @@ static int pipe_encode(zw_pipe* p, int nb)
     if (p->broken) return ZW_EDEVICE;
     HIPOK(hipSetDevice(p->ctx->device));
     static const bool trace = getenv("ZW_PIPE_TRACE") != nullptr;
-    const double T0 = now_ms();
-    g_trace = trace;
-    g_trace_t0 = T0;
-    p->p1_stats.assign(p->lanes.size(), 0);
+    p->trace = trace;
+    p->trace_t0 = now_ms();
+    p->p1_stats = std::vector<Progress>(p->lanes.size());
     int r = run_lanes(p, [&](PipeLane& L) -> int {
-        const int q = lane_encode(p, L, true, nb);
+        const int q = LaneRun(p, L, true, nb).run();
         if (trace)
             fprintf(stderr, "lane f0=%d n=%d chunk=%d x%d: done %.1f ms (per batch: fetch %.1f stats %.1f fetch2 %.1f "
                             "emit %.1f) k: %.1f %.1f %.1f %.1f\n",
-                    L.f0, L.n, L.chunk, nb, now_ms() - T0, L.hms[0], L.hms[1], L.hms[2], L.hms[3], L.kms[0], L.kms[1],
-                    L.kms[2], L.kms[3]);
+                    L.f0, L.n, L.chunk, nb, now_ms() - p->trace_t0, L.hms[HMS_FETCH], L.hms[HMS_STATS],
+                    L.hms[HMS_FETCH2], L.hms[HMS_EMIT], L.kms[KMS_RGB2YUV], L.kms[KMS_ANALYSIS], L.kms[KMS_PASS1],
+                    L.kms[KMS_PASS2]);
         return q;
     });
     pipe_collect_times(p);
@@ -1714,8 +1721,6 @@ extern "C" int zw_pipe_encode_host(zw_pipe* p, int nb, const uint8_t* const* fra
 
 extern "C" int zw_pipe_encode_repeat(zw_pipe* p, int n) { return pipe_encode(p, n); }
 
-extern "C" int zw_host_threads(void) { return host_threads(); }
-
 extern "C" int zw_pipe_launch_frames(zw_pipe* p) { return p && !p->lanes.empty() ? p->lanes[0].chunk : 0; }
 
 extern "C" int zw_pipe_lanes(zw_pipe* p) { return p ? (int)p->lanes.size() : 0; }
@@ -1723,7 +1728,7 @@ extern "C" int zw_pipe_lanes(zw_pipe* p) { return p ? (int)p->lanes.size() : 0; 
 extern "C" int zw_pipe_kernel_times(zw_pipe* p, float* ms, int n)
 {
     if (!p || !ms) return ZW_EINVAL;
-    for (int i = 0; i < n && i < 9; i++) ms[i] = p->kms[i];
+    for (int i = 0; i < n && i < PIPE_MS_COUNT; i++) ms[i] = p->kms[i];
     return ZW_OK;
 }
 
@@ -2265,12 +2270,6 @@ static int make_matrix(ZwMatrix& m, int q_dc, int q_ac, int matrix_type)
         m.zthresh[i] = ((1u << 17) - 1 - m.bias[i]) / m.iq[i];
     }
     return ZW_OK;
-}
-
-static int device_cus(int device)
-{
-    hipDeviceProp_t prop;
-    return hipGetDeviceProperties(&prop, device) == hipSuccess ? prop.multiProcessorCount : 256;
 }
 
 extern "C" int zw_transform_quant_blocks_device(zw_ctx* ctx, void* stream, size_t n, const void* d_src,

@@ -255,6 +255,58 @@ def test_pipe_encode_host(ctx, monkeypatch, nb, lanes, chunk, up, pack, w, h):
         p.close()
 
 
+_PAIRED_LANES_CHILD = r"""
+import os, sys
+sys.path[:0] = [os.path.join(sys.argv[1], "image-webp_amd"), os.path.join(sys.argv[1], "tests")]
+import oracle_lib as O
+import zwebp
+from zwebp.synth import synth_rgba
+n, w, h = 16, 208, 144
+imgs = [synth_rgba(w, h, 0x5EED7000 + i, ("natural", "noise", "flat")[i % 3]) for i in range(n)]
+refs = []
+for im in imgs:
+    rc, ref, _ = O.encode(im, w, h, 3, 75, 4)
+    assert rc == 0
+    refs.append(ref)
+ctx = zwebp.Context(0)
+p = zwebp.Pipeline(n, w, h, zwebp.ColorType.Rgba8, 75, 4, ctx=ctx)
+assert p.lanes == 2 and p.launch_frames == 3, (p.lanes, p.launch_frames)
+for i in range(n):
+    p.upload(i, imgs[i])
+p.encode_repeat(3)
+bad = [i for i in range(n) if p.output(i) != refs[i]]
+assert not bad, ("encode_repeat", bad)
+# three batches from host memory: the frames rotated by b + 1 in batch b, so every
+# batch differs and the last one (whose outputs remain) is the frames rotated by 3:
+# a stale input buffer would show
+batches = [[imgs[(i + b + 1) % n] for i in range(n)] for b in range(3)]
+p.encode_host(batches)
+bad = [i for i in range(n) if p.output(i) != refs[(i + 3) % n]]
+assert not bad, ("encode_host", bad)
+p.close()
+ctx.close()
+print("ok")
+"""
+
+
+def test_pipe_paired_lanes_batches():
+    """The headline's scheduling at a small size: two lanes, pass 1 and pass 2
+    both in frame pairs, the cross-lane pass-1 order, several batches.  16
+    frames of 208x144 (13x9 MBs), 8 a lane in chunks of 3, 3 and 2: one paired
+    launch and one unpaired ragged chunk per pass and lane.  On one pipe,
+    encode_repeat(3) from uploaded frames, then encode_host with 3 batches and
+    two uploaders a lane; every output equals the oracle's stream.  A fresh
+    process (ZW_ENC_FP is read once)."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, ZW_PIPE_LANES="2", ZW_PIPE_CHUNK="3", ZW_ENC_FP="1", ZW_ENC_ROWS="0",
+               ZW_UPLOAD_THREADS="2")
+    r = subprocess.run([sys.executable, "-c", _PAIRED_LANES_CHILD, root], env=env, capture_output=True, text=True,
+                       timeout=240)
+    assert r.returncode == 0 and "ok" in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
+
+
 @pytest.mark.parametrize("color", [zwebp.ColorType.Rgba8, zwebp.ColorType.La8])
 def test_encode_webp_batch_alpha_too_large(ctx, color):
     """An alpha input taller than 16384 rows: encode_alpha_lossless returns
