@@ -348,6 +348,23 @@ int ctx_d2h_stream(zw_ctx* c, void* dst, const void* src, size_t bytes)
 
 static void seam_trim(bool all);
 
+// The decode paths' buffers (both sets, the token parse's, the pinned staging).
+// The context stream is synchronised before its scratch goes and the token
+// stream before the token buffers; the events and streams stay.
+static void ctx_release_decode(zw_ctx* c)
+{
+    if (c->stream_) (void)hipStreamSynchronize(c->stream_);  // nothing queued may still use them
+    for (zw_ctx::DecSet& s : c->set) {
+        s.scratch.release();
+        s.upload.release();
+        std::vector<zw_ctx::RecBuf>().swap(s.recs);
+    }
+    if (c->tok_) (void)hipStreamSynchronize(c->tok_);
+    c->tok_scratch.release();
+    c->tok_recs.release();
+    for (PinBuf& p : c->pin) p.release();
+}
+
 extern "C" void zw_ctx_release_buffers(zw_ctx* c)
 {
     if (!c) return;
@@ -358,26 +375,13 @@ extern "C" void zw_ctx_release_buffers(zw_ctx* c)
         zw_pipe_destroy(c->pipe1);
         c->pipe1 = nullptr;
     }
-    for (auto& v : c->dec_recs) std::vector<zw_ctx::RecBuf>().swap(v);
     zw_dec_pool_trim();  // the decoded-frame buffers callers have already freed
     seam_trim(false);    // the idle pipelines concurrent single-frame calls shared
-    if (c->dscratch) (void)hipFree(c->dscratch);
-    if (c->dscratch1) (void)hipFree(c->dscratch1);
-    if (c->tok_) (void)hipStreamSynchronize(c->tok_);
-    if (c->dscratch2) (void)hipFree(c->dscratch2);
-    if (c->dscratch3) (void)hipFree(c->dscratch3);
-    c->dscratch = c->dscratch1 = c->dscratch2 = c->dscratch3 = nullptr;
-    c->dscratch2_cap = c->dscratch3_cap = 0;
+    ctx_release_decode(c);
     (void)hipDeviceSynchronize();  // queues may serve streams other than the context's
     for (auto& q : c->xmb_q)
         if (q.buf) (void)hipFree(q.buf);
     c->xmb_q.clear();
-    c->dscratch_cap = c->dscratch1_cap = 0;
-    for (int i = 0; i < 5; i++) {
-        pinned_free(c->hpin[i]);
-        c->hpin[i] = nullptr;
-        c->hpin_cap[i] = 0;
-    }
 }
 
 extern "C" void zw_ctx_destroy(zw_ctx* c)
@@ -396,22 +400,17 @@ void zw_ctx_free_internal(zw_ctx* c)
 {
     (void)hipSetDevice(c->device);
     zw_pipe_destroy(c->pipe1);
-    if (c->dscratch) (void)hipFree(c->dscratch);
-    if (c->dscratch1) (void)hipFree(c->dscratch1);
-    if (c->tok_) (void)hipStreamSynchronize(c->tok_);
-    if (c->dscratch2) (void)hipFree(c->dscratch2);
-    if (c->dscratch3) (void)hipFree(c->dscratch3);
+    ctx_release_decode(c);
     pinned_free(c->tok_total);
+    (void)hipDeviceSynchronize();  // queues may serve streams other than the context's
     for (auto& q : c->xmb_q)
         if (q.buf) (void)hipFree(q.buf);
     if (c->xmb_err) (void)hipHostFree((void*)c->xmb_err);
     for (hipEvent_t e : c->tok_ev)
         if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->dev_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->dev_ev1)
-        if (e) (void)hipEventDestroy(e);
-    for (void* h : c->hpin) pinned_free(h);
+    for (zw_ctx::DecSet& s : c->set)
+        for (hipEvent_t e : s.ev)
+            if (e) (void)hipEventDestroy(e);
     if (c->stream_) (void)hipStreamDestroy(c->stream_);
     if (c->copy_) (void)hipStreamDestroy(c->copy_);
     if (c->copy_ev) (void)hipEventDestroy(c->copy_ev);

@@ -14,23 +14,89 @@
 #include <thread>
 #include <vector>
 
+// Set (process-wide) once an SDMA copy timed out with the engine possibly
+// still writing its destination: from then on pinned host buffers, which are
+// the destinations of those copies, are leaked instead of freed, so a late
+// DMA write cannot land in memory the allocator has handed out again.
+extern std::atomic<bool> g_dma_poisoned;
+static inline void pinned_free(void* h)
+{
+    if (h && !g_dma_poisoned.load(std::memory_order_acquire)) (void)hipHostFree(h);
+}
+
+// A grow-only buffer a context keeps between calls: device memory (DevBuf) or
+// pinned host staging (PinBuf, freed by the poisoned-DMA rule above).
+template <bool PINNED>
+struct __attribute__((visibility("hidden"))) GrowBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    // At least `bytes` (the contents are lost when it grows); nullptr: out of memory.
+    void* reserve(size_t bytes)
+    {
+        if (cap < bytes) {
+            release();
+            const hipError_t e = PINNED ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes);
+            if (e != hipSuccess) {
+                p = nullptr;
+                return nullptr;
+            }
+            cap = bytes;
+        }
+        return p;
+    }
+    void release()
+    {
+        if (PINNED) pinned_free(p);
+        else if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+using DevBuf = GrowBuf<false>;
+using PinBuf = GrowBuf<true>;
+
+// The events of one decode buffer set, in stream order.
+enum DecEv { DEC_EV_RECON_START, DEC_EV_RECON_DONE, DEC_EV_FILTER_DONE, DEC_EV_CALLER, DEC_EV_COUNT };
+// The device token parse's events on its own stream, in the order they are
+// recorded: the upload queued, stage 1 done, the count pass and scans done, the
+// records written.
+enum TokEv { TOK_EV_START, TOK_EV_STAGE1, TOK_EV_COUNTED, TOK_EV_RECORDS, TOK_EV_COUNT };
+// Pinned staging shared by both decode buffer sets (each set has its own upload slot).
+enum DecPin {
+    PIN_DOWNLOAD,    // planes / packed images down
+    PIN_ERR_WORDS,   // the row-parallel kernels' sync / error words, the token parse's error words
+    PIN_TOK_UPLOAD,  // the device token parse's upload (modes, probabilities, token partitions)
+    PIN_COUNT
+};
+
 struct zw_ctx {
     int device;
     hipStream_t stream_ = nullptr;  // created on first use (hardware queues are scarce)
     hipStream_t copy_ = nullptr;    // decode downloads (ctx_d2h_stream), created on first use
     hipEvent_t copy_ev = nullptr;   // its completion, waited on without spinning
-    // grow-only device scratch for the single-call decode / filter entry points
-    void* dscratch = nullptr;
-    size_t dscratch_cap = 0;
-    void* dscratch1 = nullptr;  // second buffer of the pipelined decode batches
-    void* dscratch2 = nullptr;  // decode batches: the device token parse's upload, snapshots and offsets
-    size_t dscratch2_cap = 0;
-    void* dscratch3 = nullptr;  // decode batches: the device token parse's records (sized by its count pass)
-    size_t dscratch3_cap = 0;
+    // decode: per-frame worst-case record buffers, kept between chunks and calls
+    // (a parse touches only the pages it writes; reallocating them per chunk
+    // cost page faults and unmaps)
+    struct RecBuf {
+        std::unique_ptr<uint8_t[]> p;  // uninitialised: untouched pages stay unbacked
+        size_t cap = 0;
+    };
+    // One of the two buffer sets the pipelined decode batches alternate between.
+    // set[0].scratch is also the device scratch of the single-call decode /
+    // filter / transform entry points (ctx_scratch).
+    struct __attribute__((visibility("hidden"))) DecSet {
+        DevBuf scratch;  // records, tables, planes, the caller's extra (DecLayout)
+        PinBuf upload;   // the host parser's records, MB offsets and frame bases
+        hipEvent_t ev[DEC_EV_COUNT] = {};  // created on first use (blocking sync: the finisher sleeps on them)
+        std::vector<RecBuf> recs;
+    };
+    DecSet set[2];
+    PinBuf pin[PIN_COUNT];
+    DevBuf tok_scratch;  // the device token parse's upload, snapshots and offsets
+    DevBuf tok_recs;     // the device token parse's records (sized by its count pass)
     uint64_t* tok_total = nullptr;  // pinned: the count pass's record bytes
     hipStream_t tok_ = nullptr;  // the device token parse (runs beside the chunks' kernels), created on first use
-    // [0] before stage 1, [1] the records written, [2] the count pass and scans done, [3] stage 1 done
-    hipEvent_t tok_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t tok_ev[TOK_EV_COUNT] = {};
     // zw_transform_quant_mbs*_device: the I4 queue of k_xform_mb / k_xform_mb_i4,
     // one per launch stream (launches on different streams may overlap; launches
     // on one stream are ordered), its counters reset on that stream per launch
@@ -48,7 +114,6 @@ struct zw_ctx {
     volatile uint32_t* xmb_err = nullptr;  // host-mapped: k_xform_mb sets it on a queue overflow
     uint32_t* xmb_err_dev = nullptr;       // the same word as the device addresses it
     std::mutex xmb_mu;
-    size_t dscratch1_cap = 0;
     // SDMA copy engine path (HSA) for device->host fetches: ROCclr's hipMemcpy
     // D2H runs as a blit kernel, which cannot be dispatched while an encode
     // kernel holds every CU; the DMA engines need no CU.
@@ -59,17 +124,8 @@ struct zw_ctx {
     // into its destination, so every later copy of this context fails
     std::atomic<bool> poisoned{false};
     hsa_agent_t gpu_agent{}, cpu_agent{};
-    // grow-only pinned host staging (decode batch: MB records up, planes down)
-    // [0] / [2]: the two upload buffers of the pipelined decode, [1] downloads,
-    // [3] the row-parallel kernels' sync / error words, [4] the device token
-    // parse's upload (modes, probabilities, token partitions)
-    void* hpin[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t hpin_cap[5] = {0, 0, 0, 0, 0};
     // device time of the last decode batch: [0] k_dec_recon, [1] k_loopfilter,
     // [2] k_yuv2rgb (0 when the batch returned planes) (ms)
-    // ([4], [5]: around k_dec_tokl when the device parses the tokens)
-    hipEvent_t dev_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t dev_ev1[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // second buffer of the pipelined decode
     float dec_ms[3] = {0.f, 0.f, 0.f};
     float dec_tok_ms = 0.f;  // the device token parse of the last batch (0: the host parsed every frame)
     float dec_tok_stage_ms[3] = {0.f, 0.f, 0.f};  // its stage 1, count pass + offsets (+ the host's wait), record pass
@@ -88,14 +144,6 @@ struct zw_ctx {
     struct zw_pipe* pipe1 = nullptr;
     int pipe1_key[5] = {0, 0, 0, 0, 0};
     std::mutex pipe1_mu;
-    // decode: per-frame worst-case record buffers of the two pipelined buffer
-    // sets, kept between chunks and calls (a parse touches only the pages it
-    // writes; reallocating them per chunk cost page faults and unmaps)
-    struct RecBuf {
-        std::unique_ptr<uint8_t[]> p;  // uninitialised: untouched pages stay unbacked
-        size_t cap = 0;
-    };
-    std::vector<RecBuf> dec_recs[2];
 };
 
 #define HIPOK(x)                                  \
@@ -158,44 +206,8 @@ static inline void parallel_for(int n, F fn, int max_threads = 0)
 }
 
 
-// Device scratch `which` (0 or 1) of at least `bytes` owned by the context.
-static inline void* ctx_scratch(zw_ctx* c, size_t bytes, int which = 0)
-{
-    void*& p = which ? c->dscratch1 : c->dscratch;
-    size_t& cap = which ? c->dscratch1_cap : c->dscratch_cap;
-    if (cap < bytes) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
-        cap = bytes;
-    }
-    return p;
-}
-
-static inline void* ctx_scratch_rec(zw_ctx* c, size_t bytes)
-{
-    if (c->dscratch3_cap < bytes) {
-        if (c->dscratch3) (void)hipFree(c->dscratch3);
-        c->dscratch3 = nullptr;
-        c->dscratch3_cap = 0;
-        if (hipMalloc(&c->dscratch3, bytes) != hipSuccess) return nullptr;
-        c->dscratch3_cap = bytes;
-    }
-    return c->dscratch3;
-}
-
-static inline void* ctx_scratch_tok(zw_ctx* c, size_t bytes)
-{
-    if (c->dscratch2_cap < bytes) {
-        if (c->dscratch2) (void)hipFree(c->dscratch2);
-        c->dscratch2 = nullptr;
-        c->dscratch2_cap = 0;
-        if (hipMalloc(&c->dscratch2, bytes) != hipSuccess) return nullptr;
-        c->dscratch2_cap = bytes;
-    }
-    return c->dscratch2;
-}
+// Device scratch of at least `bytes` for the single-call entry points.
+static inline void* ctx_scratch(zw_ctx* c, size_t bytes) { return c->set[0].scratch.reserve(bytes); }
 
 // The context's own stream (single-call entry points); created lazily so a
 // context that only drives pipes does not hold a hardware queue.
@@ -226,29 +238,6 @@ void zw_dec_pool_trim();
 bool zw_ctx_any_alive();
 // Frees a context's resources and the context (zw_ctx_destroy minus the count).
 void zw_ctx_free_internal(zw_ctx* c);
-
-// Set (process-wide) once an SDMA copy timed out with the engine possibly
-// still writing its destination: from then on pinned host buffers, which are
-// the destinations of those copies, are leaked instead of freed, so a late
-// DMA write cannot land in memory the allocator has handed out again.
-extern std::atomic<bool> g_dma_poisoned;
-static inline void pinned_free(void* h)
-{
-    if (h && !g_dma_poisoned.load(std::memory_order_acquire)) (void)hipHostFree(h);
-}
-
-// Pinned host staging buffer `which` of at least `bytes` owned by the context.
-static inline void* ctx_pinned(zw_ctx* c, int which, size_t bytes)
-{
-    if (c->hpin_cap[which] < bytes) {
-        pinned_free(c->hpin[which]);
-        c->hpin[which] = nullptr;
-        c->hpin_cap[which] = 0;
-        if (hipHostMalloc(&c->hpin[which], bytes, hipHostMallocDefault) != hipSuccess) return nullptr;
-        c->hpin_cap[which] = bytes;
-    }
-    return c->hpin[which];
-}
 
 // Host lossless coder and container writer (zw_host_lossless.cpp).
 int zw_vp8l_encode(const uint8_t* data, size_t len, uint32_t width, uint32_t height, int color, bool predictor,

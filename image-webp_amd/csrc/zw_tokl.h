@@ -7,7 +7,7 @@
 // (zw_dbg_tokl_frame, the CPU check against the host parser).  The memory
 // interface M supplies the tables, the stream bits, the per-MB modes and the
 // record stores; the output is the packed MB records of zw_common.h ZW_DREC_*,
-// byte-identical to zw_dec_host.cpp parse_mbs.
+// byte-identical to zw_dec_parse.cpp parse_mbs.
 //
 // step() is one binary decision and everything it implies, written branch-free
 // (selects, and stores with a condition that the device turns into an
@@ -31,10 +31,15 @@
 //   Y2, Y 0..15, U 0..3, V 0..3): context bit positions in TL (top bits 0..8,
 //   left bits 16..24), the probability row base, the first position.
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// (a plain C++ compiler builds the host replay, zw_dec_parse.cpp, without HIP)
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
 #define TKL_HD __host__ __device__ __forceinline__
+#else
+#define TKL_HD inline __attribute__((always_inline))
+#endif
 
 namespace tokl {
 

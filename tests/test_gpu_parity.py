@@ -542,6 +542,38 @@ def test_decode_batch_chunked_size_change(ctx, monkeypatch):
 
 
 @pytest.mark.parametrize("tokens", ["host", "device"])
+def test_decode_timers_follow_the_batch(ctx, monkeypatch, tokens):
+    """The per-batch timers read the right events and slots: after a planes batch
+    of three chunks (both buffer sets reused) the two kernel times and the parse
+    time are positive and the RGB kernel's is 0; the device token parse's three
+    stage times are consecutive intervals of the same four events, so they sum to
+    its total; an RGB batch on the same context sets the RGB kernel time and the
+    next planes batch clears it."""
+    monkeypatch.setenv("ZW_DEC_CHUNK", "2")
+    monkeypatch.setenv("ZW_DEC_TOKENS", tokens)
+    streams = [O.encode(synth_rgba(64, 48, 0x5EED4100 + i), 64, 48, 3, 75, 4)[1] for i in range(5)]
+
+    def planes_batch():
+        assert len(zwebp.decode_batch(streams, ctx=ctx)) == 5
+        recon, lf = zwebp.decode_kernel_times(ctx=ctx)
+        parse, download, fan = zwebp.decode_stage_times(ctx=ctx)
+        print("kernel ms", recon, lf, "stage ms", parse, download, fan)
+        assert recon > 0 and lf > 0
+        assert parse > 0 and download >= 0 and fan >= 0
+        assert zwebp.decode_rgb_kernel_ms(ctx=ctx) == 0
+
+    planes_batch()
+    if tokens == "device":
+        total, stages = zwebp.decode_token_ms(ctx=ctx), zwebp.decode_token_stages(ctx=ctx)
+        print("token ms", total, stages)
+        assert total > 0 and len(stages) == 3
+        assert abs(sum(stages) - total) <= 0.05 * total
+    assert len(zwebp.decode_rgb_batch(streams, 4, ctx=ctx)) == 5
+    assert zwebp.decode_rgb_kernel_ms(ctx=ctx) > 0
+    planes_batch()
+
+
+@pytest.mark.parametrize("tokens", ["host", "device"])
 @pytest.mark.parametrize("rows", ["1", "0"])
 def test_decode_rows_and_frame_kernels(ctx, monkeypatch, rows, tokens):
     """Both reconstruction / loop-filter kernel families on the same 1080p streams
