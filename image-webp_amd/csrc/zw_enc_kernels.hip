@@ -1,7 +1,7 @@
 // zw_enc_kernels.hip -- device half of the lossy encoder (gfx950).
 //
 //   k_rgb2yuv     convert_image_yuv / convert_image_y      (decoder/yuv.rs:656, :806)
-//   k_analysis    analyze_image per-MB alpha + histogram    (encoder/analysis.rs:964)
+//   k_analysis4   analyze_image per-MB alpha + histogram    (encoder/analysis.rs:964)
 //   k_segments    k-means, segment quant, matrices, lambdas (analysis.rs:1029, :1145;
 //                 vp8.rs:2278-2388, types.rs:806)
 //   k_encode      one encode pass over a batch of frames:   (vp8.rs:1281-1488)
@@ -16,6 +16,13 @@
 // and runs on wave 0 while waves 1..NW-1 do the luma wavefront.
 #include "zw_dev.h"
 
+#include "zw_enc_rows.h"
+
+// ---------------------------------------------------------------------------
+// Compile-time knobs (make exp EXPDEFS="-DZW_...=..."), each with the
+// measurement that set its default.  The row schedule's (ZW_P1_ORDER,
+// ZW_P1_SLOWSKIP, ZW_P1_SLOW_NUM / _DEN) are in zw_enc_rows.h.
+// ---------------------------------------------------------------------------
 // Waves per workgroup of each encode pass.  Both kernels stay within 168
 // VGPRs, so three waves share each SIMD (12 per CU); ZW_NW sets both.
 #ifdef ZW_NW
@@ -29,8 +36,9 @@
 #define ZW_NW2 12
 #endif
 #define NW_MAX (ZW_NW1 > ZW_NW2 ? ZW_NW1 : ZW_NW2)
-// Issue priority of a luma wave from its slack to the row above (encode_body):
-// slack (MBs) per priority level, 0: off; pass 1's level width and cap.
+// Issue priority of a luma wave from its slack to the row above
+// (luma_issue_prio): slack (MBs) per priority level, 0: off; pass 1's level
+// width and cap.
 #ifndef ZW_DYN_PRIO
 #define ZW_DYN_PRIO 1
 #endif
@@ -40,6 +48,50 @@
 #ifndef ZW_P1_LUMA_MAX
 #define ZW_P1_LUMA_MAX 3  // (2 kept the luma waves below the chroma chain: 0.7 % slower)
 #endif
+// The chroma chain is pass 1's critical path: it takes issue priority over the
+// luma waves sharing its SIMD (measured: 47.6 -> 44.3 ms per 256 1080p frames
+// against luma-first priority at 12 waves).  Pass 1's luma waves start below
+// it: the chain sets the pass's length once 11 waves share the luma wavefront.
+#ifndef ZW_CHAIN_PRIO
+#define ZW_CHAIN_PRIO 3
+#endif
+#ifndef ZW_LUMA_PRIO
+#define ZW_LUMA_PRIO 0
+#endif
+// Pass 1's chroma chain: one wave (pair form) or two (quad form, one wave per
+// plane).  The row-parallel kernels take the two-wave chain: it bounds their
+// pass 1 (one 1080p frame: 27.7 -> 22.1 ms), and their pass-1 workgroups then
+// run two waves (the chain's two planes; two luma rows elsewhere).  The batch
+// kernels keep one chain wave: there a second one costs a luma wave and
+// measured slower (34.4 -> 35.0 ms per 256 1080p frames).
+#ifndef ZW_UVQ_CHAIN_ROWS
+#define ZW_UVQ_CHAIN_ROWS 1
+#endif
+#ifndef ZW_UVQ_CHAIN_BATCH
+#define ZW_UVQ_CHAIN_BATCH 0
+#endif
+// The per-MB stage loops of the frame-pair kernel: ZW_PAIR_UNROLL 1 emits
+// each stage twice (constant frame index), 0 once (a two-trip loop); measured
+// per 256 1080p frames: pass 2 29.80 vs 30.26 ms, pass 1 the same.
+#ifndef ZW_PAIR_UNROLL
+#define ZW_PAIR_UNROLL 1
+#endif
+// Pass 1 loads the MB's source words and alpha at the top of its iteration,
+// in flight during the wait for the row above; pass 2 fetches them one MB
+// ahead.  (Fetched ahead, the words do not stay in registers: each is spilled
+// to scratch right after its load, so the three loads run one after another,
+// each also waiting for the previous MB's stores -- vmcnt counts stores.
+// Measured per 256 1080p frames: pass 1 29.12 -> 28.98 ms loading at the top,
+// pass 2 37.38 -> 37.64 ms.)  An expression of the kernel's PASS.
+#ifndef ZW_FETCH_AHEAD
+#define ZW_FETCH_AHEAD (PASS == 2)
+#endif
+// k_analysis4: 4-MB groups per wave (measured, analysis + segments per 256
+// 1080p frames: 1 1.375, 2 1.47, 4 1.41 ms).
+#ifndef ZW_AN4_GPW
+#define ZW_AN4_GPW 1
+#endif
+
 template <int PASS> struct PassShape {
     static constexpr int NW = PASS == 1 ? ZW_NW1 : ZW_NW2;
     static constexpr int WG = NW * 64;
@@ -181,12 +233,14 @@ __global__ __launch_bounds__(256) void k_rgb2yuv_rows(const uint8_t* __restrict_
 }
 
 // ---------------------------------------------------------------------------
-// Analysis (analysis.rs:964): one wave per MB.  Lanes 0..31: luma (mode DC/TM
-// x 16 blocks), lanes 32..47: chroma (mode x 8 blocks).  Predictors use source
-// pixels; on the MB-padded planes libwebp's import/replicate rules reduce to
-// direct reads (analysis.rs:520-745).
+// Analysis (analysis.rs:964), four MBs a wave: 16 lanes an MB, lane j working
+// three of the MB's 48 (block, mode) items -- luma block j under DC and under
+// TM, chroma block j & 7 (U 0-3, V 4-7) under mode j >> 3 -- so every lane has
+// work and the four MBs' chains overlap.  Predictors use source pixels; on the
+// MB-padded planes libwebp's import/replicate rules reduce to direct reads
+// (analysis.rs:520-745).
 // ---------------------------------------------------------------------------
-// One wave per MB: the MB and its edge pixels staged in LDS.
+// An MB and its edge pixels staged in LDS.
 struct AnalysisTile {
     uint32_t y[16][4];     // luma rows, 4 packed pixels per word
     uint32_t c[2][8][2];   // U, V rows
@@ -195,259 +249,6 @@ struct AnalysisTile {
     uint8_t corner[4];     // Y, U, V
 };
 
-#ifndef ZW_AN_MPW
-#define ZW_AN_MPW 8
-#endif
-extern "C" __global__ __launch_bounds__(256) void k_analysis(const uint8_t* __restrict__ Y, const uint8_t* __restrict__ U,
-                                                             const uint8_t* __restrict__ V, int mbw, int mbh,
-                                                             size_t ysz, size_t csz, uint8_t* __restrict__ alpha,
-                                                             uint32_t* __restrict__ histo)
-{
-    __shared__ uint32_t hist[4][4][32];  // [wave][histogram][bin]
-    __shared__ AnalysisTile tile[4];
-    __shared__ uint32_t ahist[256];      // the workgroup's share of the frame's alpha histogram
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int f = blockIdx.y;
-    const int nmb = mbw * mbh;
-    ahist[threadIdx.x] = 0;
-    __syncthreads();
-    const int ys = mbw * 16, cs = mbw * 8;
-    const uint8_t* Yf = Y + (size_t)f * ysz;
-    const uint8_t* Uf = U + (size_t)f * csz;
-    const uint8_t* Vf = V + (size_t)f * csz;
-    // This lane's share of an MB and its edges (coalesced u32 loads): y = one
-    // luma word; x = a chroma word (lanes < 32), the top row (32..39) or a left
-    // pixel (40..63); x2 = the V left pixel (56..63); corner (lanes < 3).
-    // Branch-free: every lane issues the same three dword loads at lane-computed
-    // addresses (a byte is taken from its aligned dword when the MB is staged; a
-    // lane with nothing to fetch reads the frame's first word and discards it),
-    // so the next MB's loads stay in flight while this MB is analysed (a
-    // lane-divergent if-chain of loads made the compiler wait for each in turn).
-    //   y: one luma word;  x: lanes 0..31 chroma words (plane lane >> 4, row
-    //   (lane >> 1) & 7), 32..35 the luma top row, 36..39 the chroma top rows,
-    //   40..55 the luma left column (bytes), 56..63 the U left column (bytes);
-    //   z: lanes 0..2 the Y / U / V corner, 56..63 the V left column (bytes).
-    struct AnFetch {
-        uint32_t y, xw, zw;
-        uint32_t m;  // bits 0..4: x byte shift, 5: x ok, 6: x is a byte; 8..12: z shift, 13: z ok
-    };
-    auto fetch = [&](int mb) {
-        AnFetch r = {0u, 0u, 0u, 0u};
-        if (mb >= nmb) return r;
-        const int mbx = mb % mbw, mby = mb / mbw;
-        const bool ht = mby > 0, hl = mbx > 0;
-        r.y = *(const uint32_t*)(Yf + (size_t)(mby * 16 + (lane >> 2)) * ys + mbx * 16 + 4 * (lane & 3));
-        const int rr = (lane >> 1) & 7, w = lane & 1, cr = lane - 56;
-        const uint8_t* xp;
-        size_t xo;
-        bool xok = true, xbyte = false;
-        if (lane < 32) {
-            xp = lane >> 4 ? Vf : Uf;
-            xo = (size_t)(mby * 8 + rr) * cs + mbx * 8 + 4 * w;
-        } else if (lane < 36) {
-            xp = Yf;
-            xo = (size_t)(mby * 16 - 1) * ys + mbx * 16 + 4 * (lane - 32);
-            xok = ht;
-        } else if (lane < 40) {
-            xp = ((lane - 36) >> 1) ? Vf : Uf;
-            xo = (size_t)(mby * 8 - 1) * cs + mbx * 8 + 4 * w;
-            xok = ht;
-        } else if (lane < 56) {
-            xp = Yf;
-            xo = (size_t)(mby * 16 + lane - 40) * ys + mbx * 16 - 1;
-            xok = hl;
-            xbyte = true;
-        } else {
-            xp = Uf;
-            xo = (size_t)(mby * 8 + cr) * cs + mbx * 8 - 1;
-            xok = hl;
-            xbyte = true;
-        }
-        const int zsz = lane == 0 ? 16 : 8, zst = lane == 0 ? ys : cs;
-        const uint8_t* zp = lane < 3 ? (lane == 0 ? Yf : (lane == 1 ? Uf : Vf)) : Vf;
-        const size_t zo = lane < 3 ? (size_t)(mby * zsz - 1) * zst + mbx * zsz - 1 : (size_t)(mby * 8 + cr) * cs + mbx * 8 - 1;
-        const bool zok = lane < 3 ? (ht && hl) : (lane >= 56 && hl);
-        xo = xok ? xo : 0;
-        const size_t zo2 = zok ? zo : 0;
-        r.xw = *(const uint32_t*)((xok ? xp : Yf) + (xo & ~(size_t)3));
-        r.zw = *(const uint32_t*)((zok ? zp : Yf) + (zo2 & ~(size_t)3));
-        r.m = (uint32_t)(8 * (xo & 3)) | (xok ? 32u : 0u) | (xbyte ? 64u : 0u) | ((uint32_t)(8 * (zo2 & 3)) << 8) |
-              (zok ? 0x2000u : 0u);
-        return r;
-    };
-    // ZW_AN_MPW MBs per wave, the workgroup's 4 waves on adjacent MBs; each
-    // MB's loads are issued one MB ahead
-    AnFetch nx = fetch(blockIdx.x * ZW_AN_MPW * 4 + wv);
-    for (int k = 0; k < ZW_AN_MPW; k++) {
-    const int mb = (blockIdx.x * ZW_AN_MPW + k) * 4 + wv;
-    const AnFetch cur = nx;
-    if (k + 1 < ZW_AN_MPW) nx = fetch(mb + 4);
-    wsync();
-    if (mb < nmb) {
-        const int mbx = mb % mbw, mby = mb / mbw;
-        // ---- stage the MB and its edges in LDS ----
-        // tiles: [plane][row][col] with interior rows 0..15 / 0..7, top row, left column, corner
-        AnalysisTile* A = &tile[wv];
-        const bool ht = mby > 0, hl = mbx > 0;
-        const uint32_t xm = (cur.m & 32u) ? ((cur.m & 64u) ? (cur.xw >> (cur.m & 31u)) & 255u : cur.xw) : 0u;
-        const uint8_t zb = (cur.m & 0x2000u) ? (uint8_t)(cur.zw >> ((cur.m >> 8) & 31u)) : (uint8_t)0;
-        A->y[lane >> 2][lane & 3] = cur.y;
-        if (lane < 32) A->c[lane >> 4][(lane >> 1) & 7][lane & 1] = xm;
-        else if (lane < 36) A->ytop[lane - 32] = xm;
-        else if (lane < 40) A->ctop[(lane - 36) >> 1][lane & 1] = xm;
-        else if (lane < 56) A->yleft[lane - 40] = (uint8_t)xm;
-        else {
-            A->cleft[0][lane - 56] = (uint8_t)xm;
-            A->cleft[1][lane - 56] = zb;
-        }
-        if (lane < 3) A->corner[lane] = zb;
-        wsync();
-        uint8_t bins[16];
-        uint32_t z = 0;
-        int vmax = 0, hidx = 0;
-        if (lane < 48) {
-            // libwebp analysis predictors on source pixels (analysis.rs:259-490, quirk A21):
-            // lane 0..31 luma (mode = lane >> 4: DC, TM; block lane & 15), 32..47 chroma
-            // (mode (lane-32) >> 3, block (lane-32) & 7: U 0..3, V 4..7)
-            const bool luma = lane < 32;
-            const int mode = luma ? (lane >> 4) : ((lane - 32) >> 3);
-            const int b = luma ? (lane & 15) : ((lane - 32) & 7);
-            const int pl = b >> 2;  // chroma plane
-            const int bb = luma ? b : (b & 3);
-            const int bx = luma ? (bb & 3) : (bb & 1), by = luma ? (bb >> 2) : (bb >> 1);
-            // edge sums (v_sad_u8 over 4 packed bytes)
-            uint32_t st = 0, sl = 0;
-            if (luma) {
-#pragma unroll
-                for (int w = 0; w < 4; w++) {
-                    st = __builtin_amdgcn_sad_u8(A->ytop[w], 0u, st);
-                    sl = __builtin_amdgcn_sad_u8(((const uint32_t*)A->yleft)[w], 0u, sl);
-                }
-            } else {
-#pragma unroll
-                for (int w = 0; w < 2; w++) {
-                    st = __builtin_amdgcn_sad_u8(A->ctop[pl][w], 0u, st);
-                    sl = __builtin_amdgcn_sad_u8(((const uint32_t*)A->cleft[pl])[w], 0u, sl);
-                }
-            }
-            const uint32_t s2 = ht && hl ? st + sl : (ht ? 2 * st : 2 * sl);
-            const int dcv = (ht || hl) ? (luma ? (int)((s2 + 16) >> 5) : (int)((s2 + 8) >> 4)) : 0x80;
-            const int corner = A->corner[luma ? 0 : 1 + pl];
-            int d[16];
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int r = by * 4 + i;
-                const uint32_t srow = luma ? A->y[r][bx] : A->c[pl][r][bx];
-                const int L = luma ? A->yleft[r] : A->cleft[pl][r];
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const int cidx = bx * 4 + j;
-                    const uint32_t tw = luma ? A->ytop[cidx >> 2] : A->ctop[pl][cidx >> 2];
-                    const int T = (int)((tw >> (8 * (cidx & 3))) & 255u);
-                    const int tm = (ht && hl) ? clamp255(L + T - corner) : (hl ? L : (ht ? T : 129));
-                    const int p = mode == 0 ? dcv : tm;
-                    d[i * 4 + j] = (int)((srow >> (8 * j)) & 255u) - p;
-                }
-            }
-            // forward_dct_4x4 (analysis.rs:172) == dct4x4 for residuals in [-255, 255]:
-            // (X + 1812) >> 9 == (8X + 14500) >> 12 and (X + 937) >> 9 == (8X + 7500) >> 12
-            int o[16];
-            fdct16_pk(d, o);
-            hidx = luma ? mode : 2 + mode;
-#pragma unroll
-            for (int k = 0; k < 16; k++) {
-                bins[k] = (uint8_t)min(iabs(o[k]) >> 3, 31);
-                z += bins[k] == 0;
-                vmax = max(vmax, (int)bins[k]);
-            }
-        }
-        // Fast path: when bin 0 holds at least half of a histogram's
-        // coefficients (256 luma, 128 chroma), no other bin can exceed it, so
-        // max_value = that count and last_non_zero = the largest bin index.
-        // Sums over the 8-lane groups, then the luma 16-lane groups.
-        // (DPP: quad xor 1, quad xor 2, row half mirror give each 8-lane group's
-        // total in all its lanes; the row mirror then pairs the row's two groups)
-        uint32_t zs = z;
-        int vm = vmax;
-        zs += (uint32_t)DPP((int)zs, 0xB1);
-        vm = max(vm, DPP(vm, 0xB1));
-        zs += (uint32_t)DPP((int)zs, 0x4E);
-        vm = max(vm, DPP(vm, 0x4E));
-        zs += (uint32_t)DPP((int)zs, 0x141);
-        vm = max(vm, DPP(vm, 0x141));
-        {
-            const uint32_t zo = (uint32_t)DPP((int)zs, 0x140);
-            const int vo = DPP(vm, 0x140);
-            if (lane < 32) {
-                zs += zo;
-                vm = max(vm, vo);
-            }
-        }
-        const uint32_t ncoef = lane < 32 ? 256u : 128u;
-        const bool slow = __ballot(lane < 48 && 2 * zs < ncoef) != 0ull;
-        if (slow) {
-            // bin 0 holds most coefficients: count it in the lane, add the rest
-            // with (far less contended) LDS atomics
-            for (int i = lane; i < 128; i += 64) (&hist[wv][0][0])[i] = 0;
-            wsync();
-            if (lane < 48) {
-#pragma unroll
-                for (int k = 0; k < 16; k++)
-                    if (bins[k]) atomicAdd(&hist[wv][hidx][bins[k]], 1u);
-                if (z) atomicAdd(&hist[wv][hidx][0], z);
-            }
-            wsync();
-        }
-        // per histogram: max count and last non-empty bin (get_alpha,
-        // analysis.rs:160), two histograms per pass, lane = (histogram, bin)
-        int av[4];
-        if (!slow) {
-            const int ah = zs > 1 ? (int)(510u * (uint32_t)vm / zs) : 0;
-            av[0] = __builtin_amdgcn_readlane(ah, 0);
-            av[1] = __builtin_amdgcn_readlane(ah, 16);
-            av[2] = __builtin_amdgcn_readlane(ah, 32);
-            av[3] = __builtin_amdgcn_readlane(ah, 40);
-        } else {
-#pragma unroll
-            for (int ps = 0; ps < 2; ps++) {
-                const uint32_t c = hist[wv][2 * ps + (lane >> 5)][lane & 31];
-                uint32_t mx = c;
-                mx = max(mx, (uint32_t)DPP((int)mx, 0xB1));
-                mx = max(mx, (uint32_t)DPP((int)mx, 0x4E));
-                mx = max(mx, (uint32_t)DPP((int)mx, 0x141));
-                mx = max(mx, (uint32_t)DPP((int)mx, 0x140));
-                mx = max(mx, (uint32_t)__shfl_xor((int)mx, 16));
-                const uint32_t half = (uint32_t)(__ballot(c > 0) >> (lane & 32));
-                const int lnz = half ? 31 - __clz((int)half) : 1;
-                const int ah = mx > 1 ? (int)(510u * (uint32_t)lnz / mx) : 0;
-                av[2 * ps] = __builtin_amdgcn_readlane(ah, 0);
-                av[2 * ps + 1] = __builtin_amdgcn_readlane(ah, 32);
-            }
-        }
-        const int a0 = av[0], a1 = av[1], a2 = av[2], a3 = av[3];
-        if (lane == 0) {
-            int best = max(-1, max(a0, a1));
-            int buv = max(-1, max(a2, a3));
-            int al = (3 * best + buv + 2) >> 2;
-            al = 255 - al;
-            al = al < 0 ? 0 : (al > 255 ? 255 : al);
-            alpha[(size_t)f * nmb + mb] = (uint8_t)al;
-            atomicAdd(&ahist[al], 1u);
-        }
-    }
-    }
-    __syncthreads();
-    const uint32_t c = ahist[threadIdx.x];
-    if (c) atomicAdd(&histo[(size_t)f * 256 + threadIdx.x], c);
-}
-
-// ---------------------------------------------------------------------------
-// The same analysis, four MBs a wave (ZW_AN_FORM 4): 16 lanes an MB, lane j
-// working three of the MB's 48 (block, mode) items -- luma block j under DC
-// and under TM, chroma block j & 7 (U 0-3, V 4-7) under mode j >> 3 -- so every
-// lane has work and the four MBs' chains overlap.  Items, histograms and the
-// alpha are those of k_analysis above, computed in the same order.
-// ---------------------------------------------------------------------------
 // One item: its 16 coefficient bins (min(|c| >> 3, 31)), the count of bin 0 and the largest bin.
 DI void an_item(const AnalysisTile* A, bool luma, int mode, int b, bool ht, bool hl, int bins[16], int& z, int& vmax)
 {
@@ -517,9 +318,6 @@ DI int max16(int v)
 }
 typedef unsigned an_v4u __attribute__((ext_vector_type(4)));
 typedef unsigned an_v2u __attribute__((ext_vector_type(2)));
-#ifndef ZW_AN4_GPW
-#define ZW_AN4_GPW 1  // 4-MB groups per wave (measured, analysis + segments per 256 1080p frames: 1 1.375, 2 1.47, 4 1.41 ms)
-#endif
 extern "C" __global__ __launch_bounds__(256) void k_analysis4(const uint8_t* __restrict__ Y, const uint8_t* __restrict__ U,
                                                               const uint8_t* __restrict__ V, int mbw, int mbh,
                                                               size_t ysz, size_t csz, uint8_t* __restrict__ alpha,
@@ -601,7 +399,7 @@ extern "C" __global__ __launch_bounds__(256) void k_analysis4(const uint8_t* __r
         // the bin-0 count and the largest bin
         const int z0 = red16(zA), z1 = red16(zB), z23 = an_red8(zC);
         const int v0 = max16(vA), v1 = max16(vB), v23 = max8(vC);
-        // fast path (k_analysis): bin 0 holding at least half of a histogram's
+        // fast path: bin 0 holding at least half of a histogram's
         // coefficients is its largest count, and the last non-empty bin is the largest bin
         const bool ok = 2 * z0 >= 256 && 2 * z1 >= 256 && 2 * z23 >= 128;
         int a0, a1, a23;
@@ -749,7 +547,7 @@ __device__ void segment_init(ZwSegment& s, int qi, int delta)
 }
 
 // Consumes the frame's alpha histogram and clears it for the next launch of
-// k_analysis (zeroed once at pipeline creation; no per-launch memset blit).
+// k_analysis4 (zeroed once at pipeline creation; no per-launch memset blit).
 extern "C" __global__ void k_segments(uint32_t* __restrict__ histo, const ZwFrameParams* __restrict__ tmpl,
                                       ZwFrameParams* __restrict__ params, int nframes)
 {
@@ -1616,6 +1414,24 @@ DI int rcost_quad(const int av[4], int q, int ctx0, int ctype, const LdsTables* 
     return csel(last < 0, head_none[1], head_none[0] + sum + tail);  // (no divergent branch)
 }
 
+// rank = #{lanes of the 16-lane row with a smaller key}: per rotation the
+// borrow of a DPP subtraction (keys are in [0, 2^31), so the borrow is
+// rot(key) < key) into VCC, then an add-with-carry
+DI int rank16(int key)
+{
+    int rank = 0, scratch_;
+#define ZW_RANK_STEP(R) "v_sub_co_u32_dpp %1, vcc, %2, %2 row_ror:" #R " row_mask:0xf bank_mask:0xf\n" \
+                        "v_addc_co_u32_e32 %0, vcc, 0, %0, vcc\n"
+    asm volatile("s_nop 1\n" ZW_RANK_STEP(1) ZW_RANK_STEP(2) ZW_RANK_STEP(3) ZW_RANK_STEP(4) ZW_RANK_STEP(5)
+                     ZW_RANK_STEP(6) ZW_RANK_STEP(7) ZW_RANK_STEP(8) ZW_RANK_STEP(9) ZW_RANK_STEP(10)
+                         ZW_RANK_STEP(11) ZW_RANK_STEP(12) ZW_RANK_STEP(13) ZW_RANK_STEP(14) ZW_RANK_STEP(15)
+                 : "+v"(rank), "=&v"(scratch_)
+                 : "v"(key)
+                 : "vcc");
+#undef ZW_RANK_STEP
+    return rank;
+}
+
 // Candidate evaluation of an I4 step in quad form (K <= 4: methods 0-4).  The
 // step's candidate set -- the K modes of smallest prediction SSE per block,
 // `rank` from the pair layout -- is evaluated with four lanes per (block,
@@ -1825,24 +1641,9 @@ __device__ __forceinline__ void i4_step(const Ctx& C, const int* sbx, const int*
     }
     pse = hx_sum(pse);
     const int key = m < 10 ? (pse << 4) | m : 0x7fffffff;
-    // rank = #{lanes of the 16-lane row with a smaller key}: per rotation the
-    // borrow of a DPP subtraction (keys are in [0, 2^31), so the borrow is
-    // rot(key) < key) into VCC, then an add-with-carry
-    int rank = 0, scratch_;
-#define ZW_RANK_STEP(R) "v_sub_co_u32_dpp %1, vcc, %2, %2 row_ror:" #R " row_mask:0xf bank_mask:0xf\n" \
-                        "v_addc_co_u32_e32 %0, vcc, 0, %0, vcc\n"
-    asm volatile("s_nop 1\n" ZW_RANK_STEP(1) ZW_RANK_STEP(2) ZW_RANK_STEP(3) ZW_RANK_STEP(4) ZW_RANK_STEP(5)
-                     ZW_RANK_STEP(6) ZW_RANK_STEP(7) ZW_RANK_STEP(8) ZW_RANK_STEP(9) ZW_RANK_STEP(10)
-                         ZW_RANK_STEP(11) ZW_RANK_STEP(12) ZW_RANK_STEP(13) ZW_RANK_STEP(14) ZW_RANK_STEP(15)
-                 : "+v"(rank), "=&v"(scratch_)
-                 : "v"(key)
-                 : "vcc");
-#undef ZW_RANK_STEP
+    const int rank = rank16(key);
     PH_MARK_L(11, l, 0);
-#ifndef ZW_I4_QUAD
-#define ZW_I4_QUAD 1
-#endif
-    if (ZW_I4_QUAD && K <= 4) {
+    if (K <= 4) {
         i4_cand_quad<PASS, NB>(C, sbx, sby, x0, y0, tctx, lctx, nzc, K, rank, vp, ap01, ap32, st, keep);
         return;
     }
@@ -1886,19 +1687,12 @@ __device__ __forceinline__ void i4_step(const Ctx& C, const int* sbx, const int*
     const bool elig = m < 10 && rank < K;
     // the eligible lane of smallest (score, rank) in each slot's row: the
     // reference's first strict minimum over its candidates in SSE order
-    unsigned long long win;
-    if (K <= 4) {
-        const uint32_t key2 = elig ? (score << 2) | (uint32_t)rank : 0xffffffffu;
-        const uint32_t kmin = min16u(key2);
-        win = __ballot(key2 == kmin);
-    } else {
-        // (DPP reads other lanes: every min16u runs with the whole wave active)
-        const uint32_t sk = elig ? score : 0xffffffffu;
-        const uint32_t smin = min16u(sk);
-        const uint32_t rk = sk == smin ? (uint32_t)rank : 0xffffffffu;
-        const uint32_t rmin = min16u(rk);
-        win = __ballot(rk == rmin && sk == smin);
-    }
+    // (DPP reads other lanes: every min16u runs with the whole wave active)
+    const uint32_t sk = elig ? score : 0xffffffffu;
+    const uint32_t smin = min16u(sk);
+    const uint32_t rk = sk == smin ? (uint32_t)rank : 0xffffffffu;
+    const uint32_t rmin = min16u(rk);
+    const unsigned long long win = __ballot(rk == rmin && sk == smin);
     PH_MARK_L(12, l, 0);
     int bmode[NB];
 #pragma unroll
@@ -2146,16 +1940,7 @@ DI void i4p_step(const Ctx& CA, const Ctx& CB, const int* sbx, const int* sby, i
         pse = dot2v(d32, d32, pse);
     }
     const int key = m < 10 ? (pse << 4) | m : 0x7fffffff;
-    int rank = 0, scratch_;
-#define ZW_RANK_STEP(R) "v_sub_co_u32_dpp %1, vcc, %2, %2 row_ror:" #R " row_mask:0xf bank_mask:0xf\n" \
-                        "v_addc_co_u32_e32 %0, vcc, 0, %0, vcc\n"
-    asm volatile("s_nop 1\n" ZW_RANK_STEP(1) ZW_RANK_STEP(2) ZW_RANK_STEP(3) ZW_RANK_STEP(4) ZW_RANK_STEP(5)
-                     ZW_RANK_STEP(6) ZW_RANK_STEP(7) ZW_RANK_STEP(8) ZW_RANK_STEP(9) ZW_RANK_STEP(10)
-                         ZW_RANK_STEP(11) ZW_RANK_STEP(12) ZW_RANK_STEP(13) ZW_RANK_STEP(14) ZW_RANK_STEP(15)
-                 : "+v"(rank), "=&v"(scratch_)
-                 : "v"(key)
-                 : "vcc");
-#undef ZW_RANK_STEP
+    const int rank = rank16(key);
     PH_MARK_L(11, l, 0);
     // candidate modes: k-th of each (MB, slot) group, four bits each, group g at bit 16 g
     unsigned long long modes = 0;
@@ -3092,27 +2877,9 @@ DI void row_publish(int* prog, int val)
     __builtin_amdgcn_wave_barrier();
 }
 
-// Pass 1's chroma chain: one wave (pair form) or two (quad form, one wave per
-// plane).  The row-parallel kernels take the two-wave chain: it bounds their
-// pass 1 (one 1080p frame: 27.7 -> 22.1 ms), and their pass-1 workgroups then
-// run two waves (the chain's two planes; two luma rows elsewhere).  The batch
-// kernels keep one chain wave: there a second one costs a luma wave and
-// measured slower (34.4 -> 35.0 ms per 256 1080p frames).
-#ifndef ZW_UVQ_CHAIN_ROWS
-#define ZW_UVQ_CHAIN_ROWS 1
-#endif
-#ifndef ZW_UVQ_CHAIN_BATCH
-#define ZW_UVQ_CHAIN_BATCH 0
-#endif
 template <bool ROWS> struct ChainShape {
     static constexpr int NCH = (ROWS ? ZW_UVQ_CHAIN_ROWS : ZW_UVQ_CHAIN_BATCH) ? 2 : 1;
 };
-// the per-MB stage loops of the frame-pair kernel: ZW_PAIR_UNROLL 1 emits
-// each stage twice (constant frame index), 0 once (a two-trip loop); measured
-// per 256 1080p frames: pass 2 29.80 vs 30.26 ms, pass 1 the same
-#ifndef ZW_PAIR_UNROLL
-#define ZW_PAIR_UNROLL 1
-#endif
 #if ZW_PAIR_UNROLL
 #define ZW_PAIR_LOOP _Pragma("unroll")
 #else
@@ -3122,23 +2889,75 @@ template <int PASS> struct RowsShape {
     static constexpr int NW = PASS == 1 ? ChainShape<true>::NCH : 1;
 };
 
-// Bytes of the frame-wide row arrays a workgroup keeps in LDS: top_y, top_u,
-// top_v, top_c, top_derr.  The batch kernels (one workgroup per frame) keep all
-// of them; in the row-parallel kernels the luma waves work from per-MB windows
-// of the global row state, and only pass 1's chroma chain keeps top_u / top_v /
-// top_derr, so their LDS no longer grows with the width (which is what bounded
-// the encodable width: 1 568 MBs with the batch shapes, any u16 width here).
-struct TopLds {
-    size_t y, u, v, c, d;
-    __host__ __device__ TopLds(int mbw, bool rows, int pass)
+constexpr size_t a16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// The dynamic LDS of an encode workgroup: the sizes of its regions, read by
+// the kernel (encode_body carves the regions in the order of bytes()'s sum) and
+// by the host (bytes() sizes the launch, the widest encodable frame and whether
+// frame pairs fit).  Per frame of the workgroup: the tables (sT), the frame's
+// 4 segments (sS), the alpha map (sL) and the top rows (sy, su, sv, sc, sd);
+// per wave: WaveLds (sW) and, in frame pairs, a second MbLds (sM); then the
+// progress words and the two-wave chroma chain's exchange words.
+//
+// Of the frame-wide row arrays (top_y, top_u, top_v, top_c, top_derr) the batch
+// kernels (one workgroup per frame) keep all; in the row-parallel kernels the
+// luma waves work from per-MB windows of the global row state, and only pass
+// 1's chroma chain keeps top_u / top_v / top_derr, so their LDS no longer grows
+// with the width (which is what bounded the encodable width:
+// zwk_encode_max_mbw, 1 560 MBs with the batch shapes, any u16 width here).
+struct EncLds {
+    static constexpr size_t sT = a16(sizeof(LdsTables)), sS = a16(4 * sizeof(ZwSegment)), sL = 256;
+    static constexpr size_t sW = a16(sizeof(WaveLds)), sM = a16(sizeof(MbLds));
+    size_t sy, su, sv, sc, sd;  // the top-row arrays
+    static constexpr size_t sProgress = 64, sXch = 256;
+    __host__ __device__ EncLds(int mbw, bool rows, int pass)
     {
         const bool all = !rows, chain = rows && pass == 1;
-        y = all ? (((size_t)mbw * 16 + 48 + 15) & ~(size_t)15) : 0;
-        u = v = all || chain ? (((size_t)mbw * 8 + 48 + 15) & ~(size_t)15) : 0;
-        c = all ? (((size_t)mbw * 12 + 15) & ~(size_t)15) : 0;
-        d = all || chain ? (((size_t)mbw * 4 + 15) & ~(size_t)15) : 0;
+        sy = all ? (((size_t)mbw * 16 + 48 + 15) & ~(size_t)15) : 0;
+        su = sv = all || chain ? (((size_t)mbw * 8 + 48 + 15) & ~(size_t)15) : 0;
+        sc = all ? (((size_t)mbw * 12 + 15) & ~(size_t)15) : 0;
+        sd = all || chain ? (((size_t)mbw * 4 + 15) & ~(size_t)15) : 0;
+    }
+    __host__ __device__ size_t bytes(int nw, int fp) const
+    {
+        return sT * fp + sS * fp + sL * fp + sW * nw + (fp == 2 ? sM * nw : 0) + sProgress + sXch +
+               (sy + su + sv + sc + sd) * fp;
     }
 };
+static_assert(NW_MAX * sizeof(int) <= 64, "the progress words");
+
+// A wave starts an MB row: the left borders and contexts of its first MB.
+DI void row_start(MbLds* M, int lane)
+{
+    if (lane < 20) M->left_y[lane] = 129;
+    if (lane < 12) {
+        M->left_u[lane] = 129;
+        M->left_v[lane] = 129;
+        M->left_c[lane] = 0;
+    }
+    if (lane < 4) M->left_derr[lane] = 0;
+}
+
+// Issue priority of a batch kernel's luma wave from its slack to the row above
+// (which wave prevw works; none at row 0).  VALU issue is arbitrated by
+// priority, then wave age: at equal priority the youngest waves of each SIMD
+// run slowest and every row behind theirs waits on them (35 % of the oldest
+// waves' time).  A row that trails the row above by more than the two-MB
+// minimum is the one later rows wait for, so it issues first.
+template <int PASS> DI void luma_issue_prio(const int* progress, int prevw, int mbx, int mby, int mbw)
+{
+#if ZW_DYN_PRIO > 0
+    int slack = mbw;
+    if (mby > 0) {
+        const int v = __builtin_amdgcn_readfirstlane(
+            __hip_atomic_load(&progress[prevw], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+        if ((v >> 16) == mby - 1) slack = (v & 0xffff) - mbx - 1;
+    }
+    constexpr int dp = PASS == 1 ? ZW_DYN_PRIO1 : ZW_DYN_PRIO;
+    const int p = slack >= dp * 3 ? 3 : (slack >= dp * 2 ? 2 : (slack >= dp ? 1 : 0));
+    set_prio(PASS == 1 ? min(p, ZW_P1_LUMA_MAX) : p);
+#endif
+}
 
 template <int PASS, bool ROWS, int FP = 1>
 __device__ __forceinline__ void encode_body(const EncArgs& a)
@@ -3157,35 +2976,35 @@ __device__ __forceinline__ void encode_body(const EncArgs& a)
     const int mbw = a.mbw, mbh = a.mbh;
     const ZwFrameParams* P = a.params + f;
     // carve LDS
+    // (the regions in the order of EncLds::bytes())
+    const EncLds L(mbw, ROWS, PASS);
     size_t off = 0;
     // (per frame of the workgroup: the tables, segments, alpha map and the top rows)
-    constexpr size_t sT = (sizeof(LdsTables) + 15) & ~(size_t)15, sS = (4 * sizeof(ZwSegment) + 15) & ~(size_t)15;
     LdsTables* T = (LdsTables*)(smem + off);
-    off += sT * FP;
+    off += L.sT * FP;
     ZwSegment* Sl = (ZwSegment*)(smem + off);  // the frame's 4 segments (matrices, lambdas, sharpening)
-    off += sS * FP;
+    off += L.sS * FP;
     uint8_t* seg_lut = smem + off;  // alpha -> segment (zeros when segmentation is off)
-    off += 256 * FP;
+    off += L.sL * FP;
     WaveLds* Wall = (WaveLds*)(smem + off);
-    off += ((sizeof(WaveLds) + 15) & ~(size_t)15) * NW;
+    off += L.sW * NW;
     MbLds* Mall2 = (MbLds*)(smem + off);  // frame pairs: the second frame's per-MB state
-    off += PAIR ? ((sizeof(MbLds) + 15) & ~(size_t)15) * NW : 0;
+    off += PAIR ? L.sM * NW : 0;
     int* progress = (int*)(smem + off);
-    off += 64;
+    off += L.sProgress;
     int* xch = (int*)(smem + off);  // two-wave chroma chain: [plane][2][12] exchange words, then 2 flags
     int* xflag = xch + 48;
-    off += 256;
-    const TopLds TS(mbw, ROWS, PASS);
+    off += L.sXch;
     uint8_t* top_y = smem + off;
-    off += TS.y * FP;
+    off += L.sy * FP;
     uint8_t* top_u = smem + off;
-    off += TS.u * FP;
+    off += L.su * FP;
     uint8_t* top_v = smem + off;
-    off += TS.v * FP;
+    off += L.sv * FP;
     uint8_t* top_c = smem + off;  // [mbw][12]: y2, y[4], u[2], v[2]
-    off += TS.c * FP;
+    off += L.sc * FP;
     int8_t* top_derr = (int8_t*)(smem + off);  // [mbw][4]
-    WaveLds* W = (WaveLds*)((uint8_t*)Wall + ((sizeof(WaveLds) + 15) & ~(size_t)15) * wv);
+    WaveLds* W = (WaveLds*)((uint8_t*)Wall + L.sW * wv);
     // row-parallel: is this workgroup pass 1's chroma chain (it keeps the
     // frame-wide top_u/v/derr in LDS), and the frame's global row state
     const bool chain_wg = PASS == 1 && (ROWS ? blockIdx.x == 0 : wv < NCW);
@@ -3200,9 +3019,9 @@ __device__ __forceinline__ void encode_body(const EncArgs& a)
         if (fr >= nf) break;
         const int ff = f + fr;
         const ZwFrameParams* Pf = a.params + ff;
-        LdsTables* Tf = (LdsTables*)((uint8_t*)T + sT * fr);
-        ZwSegment* Sf = (ZwSegment*)((uint8_t*)Sl + sS * fr);
-        uint8_t* lut = seg_lut + 256 * fr;
+        LdsTables* Tf = (LdsTables*)((uint8_t*)T + L.sT * fr);
+        ZwSegment* Sf = (ZwSegment*)((uint8_t*)Sl + L.sS * fr);
+        uint8_t* lut = seg_lut + L.sL * fr;
         for (int i = threadIdx.x; i < (int)(sizeof(Tf->lc) / 2); i += WG)
             (&Tf->lc[0][0][0][0])[i] = a.lcost ? (&a.lcost[ff].lc[0][0][0][0])[i] : 0;
         for (int i = threadIdx.x; i < 96; i += WG) {
@@ -3216,11 +3035,11 @@ __device__ __forceinline__ void encode_body(const EncArgs& a)
         for (int i = threadIdx.x; i < 256; i += WG) lut[i] = Pf->seg_enabled ? Pf->seg_map_lut[i] : 0;
         load_static_tables(Tf, threadIdx.x, WG, &Pf->probs[0][0][0][0]);
         if (!ROWS || chain_wg) {
-            uint8_t* ty = top_y + TS.y * fr;
-            uint8_t* tu = top_u + TS.u * fr;
-            uint8_t* tv = top_v + TS.v * fr;
-            uint8_t* tcx = top_c + TS.c * fr;
-            int8_t* td = top_derr + TS.d * fr;
+            uint8_t* ty = top_y + L.sy * fr;
+            uint8_t* tu = top_u + L.su * fr;
+            uint8_t* tv = top_v + L.sv * fr;
+            uint8_t* tcx = top_c + L.sc * fr;
+            int8_t* td = top_derr + L.sd * fr;
             if (!ROWS) {
                 for (int i = threadIdx.x; i < mbw * 16 + 48; i += WG) ty[i] = 127;
                 for (int i = threadIdx.x; i < mbw * 12; i += WG) tcx[i] = 0;
@@ -3270,13 +3089,7 @@ __device__ __forceinline__ void encode_body(const EncArgs& a)
 #endif
 
     if (chain_wg) {
-        // ---- pass-1 chroma raster chain ----
-        // the chain is pass 1's critical path: it takes issue priority over the
-        // luma waves sharing its SIMD (measured: 47.6 -> 44.3 ms per 256 1080p
-        // frames against luma-first priority at 12 waves)
-#ifndef ZW_CHAIN_PRIO
-#define ZW_CHAIN_PRIO 3
-#endif
+        // ---- pass-1 chroma raster chain ---- (issue priority: see ZW_CHAIN_PRIO)
         __builtin_amdgcn_s_setprio(ZW_CHAIN_PRIO);
         // frame pairs: chain wave k works frame f + k
         const int cfr = PAIR ? wv : 0;
@@ -3285,15 +3098,15 @@ __device__ __forceinline__ void encode_body(const EncArgs& a)
             return;
         }
         const int fc = f + cfr;
-        const uint8_t* const lutc = seg_lut + 256 * cfr;
-        int8_t* const tdc = top_derr + TS.d * cfr;
+        const uint8_t* const lutc = seg_lut + L.sL * cfr;
+        int8_t* const tdc = top_derr + L.sd * cfr;
         if (PAIR) {
             C.f = fc;
             C.P = a.params + fc;
-            C.T = (const LdsTables*)((const uint8_t*)T + sT * cfr);
-            C.Sl = (const ZwSegment*)((const uint8_t*)Sl + sS * cfr);
-            C.top_u = top_u + TS.u * cfr;
-            C.top_v = top_v + TS.v * cfr;
+            C.T = (const LdsTables*)((const uint8_t*)T + L.sT * cfr);
+            C.Sl = (const ZwSegment*)((const uint8_t*)Sl + L.sS * cfr);
+            C.top_u = top_u + L.su * cfr;
+            C.top_v = top_v + L.sv * cfr;
             C.top_derr = tdc;
             C.method = __builtin_amdgcn_readfirstlane(C.P->method);
         }
@@ -3392,78 +3205,12 @@ __device__ __forceinline__ void encode_body(const EncArgs& a)
         return;
     }
 
-    // Pass 1 luma waves: below the chroma chain (ZW_CHAIN_PRIO), which sets the
-    // pass's length once 11 waves share the luma wavefront.
-#ifndef ZW_LUMA_PRIO
-#define ZW_LUMA_PRIO 0
-#endif
     if (PASS == 1) __builtin_amdgcn_s_setprio(ZW_LUMA_PRIO);
-    const int nrw = PASS == 1 ? NW - NCH : NW;  // waves on the luma wavefront
-    // Row k of each round of nrw rows goes to wave luma_wave(k).  In pass 1 the
-    // luma waves that share SIMD 0 with the chroma chain (issue priority 3)
-    // run slowest, and every later row of a round waits on a slow row: they
-    // take the last rows of each round, which only the next round's first
-    // row follows, with a round of slack.
-#ifndef ZW_P1_ORDER
-#define ZW_P1_ORDER 1
-#endif
-    auto p1_before = [](int v, int w) {  // wave v takes its row of a round before wave w
-        const bool sv = (v & 3) < NCH, sw = (w & 3) < NCH;
-        return (ZW_P1_ORDER && sv != sw) ? sw : v < w;
-    };
-    auto luma_rank = [&](int w) {
-        if (PASS == 2) return w;
-        int r = 0;
-        for (int v = NCH; v < NW; v++) r += (int)p1_before(v, w);
-        return r;
-    };
-    auto luma_wave = [&](int k) {
-        if (PASS == 2) return k;
-        int w = NCH;
-        for (int v = NCH; v < NW; v++)
-            if (luma_rank(v) == k) w = v;
-        return w;
-    };
-    // ZW_P1_SLOWSKIP (pass 1, batch shape): the luma waves on SIMD 0 (beside
-    // the chain) take fewer rows.  Rows go out in rounds: the nfast rows of the
-    // other SIMDs' waves, then the round's share of SIMD-0 rows (the SIMD-0
-    // waves in turn), ZW_P1_SLOW_NUM SIMD-0 rows per ZW_P1_SLOW_DEN rounds.  So
-    // SIMD 0 carries the chain plus fewer luma rows, and its rows keep pace
-    // with the rest instead of throttling every row behind them.
-#ifndef ZW_P1_SLOWSKIP
-#define ZW_P1_SLOWSKIP 1
-#endif
-#ifndef ZW_P1_SLOW_NUM
-#define ZW_P1_SLOW_NUM 1  // re-tuned in round 4 (1080p, 256 frames, one lane): 1/1 28.2-28.3 ms, 3/2 28.8-29.0,
-#endif                    // 2/3 29.0-29.1, 1/2 29.2, 4/3 29.8, 0/1 29.9, 2/1 31.7
-#ifndef ZW_P1_SLOW_DEN
-#define ZW_P1_SLOW_DEN 1
-#endif
-    constexpr bool skip_mode = ZW_P1_SLOWSKIP && PASS == 1 && !ROWS && NCH == 1 && NW > 4;
-    constexpr int nslow = (NW - 1) / 4 > 0 ? (NW - 1) / 4 : 1;  // luma waves on SIMD 0: 4, 8, ..
-    constexpr int nfast = NW - NCH - (NW - 1) / 4;             // luma waves on SIMDs 1..3
-    auto fast_wave = [](int i) { return i + 1 + i / 3; };
-    auto wave_of_row = [&](int y) {
-        if (!skip_mode) return luma_wave(y % (nrw > 0 ? nrw : 1));
-        constexpr int L = ZW_P1_SLOW_DEN * nfast + ZW_P1_SLOW_NUM;
-        int r = y % L, before = (y / L) * ZW_P1_SLOW_NUM;
-        for (int k = 0; k < ZW_P1_SLOW_DEN; k++) {
-            const int sk = ((k + 1) * ZW_P1_SLOW_NUM) / ZW_P1_SLOW_DEN - (k * ZW_P1_SLOW_NUM) / ZW_P1_SLOW_DEN;
-            if (r < nfast) return fast_wave(r);
-            r -= nfast;
-            if (r < sk) return 4 * (1 + (before + r) % nslow);
-            r -= sk;
-            before += sk;
-        }
-        return 0;  // unreachable
-    };
-    // skip mode: the wave's next row after `y`
-    auto next_row = [&](int y) {
-        for (y++; y < mbh; y++)
-            if (wave_of_row(y) == wv) break;
-        return y;
-    };
-    const int rw = ROWS ? 0 : (skip_mode ? next_row(-1) : luma_rank(wv));
+    // which wave works which row (zw_enc_rows.h)
+    using RS = RowSchedule<PASS, ROWS, NW, NCH>;
+    constexpr bool skip_mode = RS::skip_mode;
+    constexpr int nrw = RS::nrw;
+    const int rw = ROWS ? 0 : RS::first_row(wv, mbh);
     if (ROWS) {
         // the wave's window stands in for the frame-wide top arrays (offsets 0)
         C.top_y = W->win_y;
@@ -3562,23 +3309,15 @@ __device__ __forceinline__ void encode_body(const EncArgs& a)
         const bool trel1 = PASS == 2 && nf == 2 && __builtin_amdgcn_readfirstlane(a.params[f + 1].do_trellis);
         const bool keep1 = !trel1 && (PASS == 1 || a.dbg == nullptr);
         // the luma waves (pass 1: after the chain waves) take the rows in turn
-        constexpr int NL = NW - NCW;
+        using RP = RowSchedule<PASS, ROWS, NW, NCW, true>;
         const bool same_k = nf == 1 || (meth1 == C.method && trel1 == trel);
         for (int it = 0;; it++) {
-            const int mby = (wv - NCW) + it * NL;
+            const int mby = RP::first_row(wv, mbh) + it * RP::nrw;
             if (mby >= mbh) break;
 #pragma unroll
-            for (int fr = 0; fr < 2; fr++) {
-                MbLds* M = Mp[fr];
-                if (lane < 20) M->left_y[lane] = 129;
-                if (lane < 12) {
-                    M->left_u[lane] = M->left_v[lane] = 129;
-                    M->left_c[lane] = 0;
-                }
-                if (lane < 4) M->left_derr[lane] = 0;
-            }
+            for (int fr = 0; fr < 2; fr++) row_start(Mp[fr], lane);
             wsync();
-            const int prevw = mby > 0 ? NCW + (mby - 1) % NL : 0;
+            const int prevw = mby > 0 ? RP::wave_of_row(mby - 1) : 0;
             auto wait_above = [&](int need) {
                 if (mby > 0) wait_row(progress, prevw, (mby - 1) * 65536 + need);
             };
@@ -3593,13 +3332,13 @@ __device__ __forceinline__ void encode_body(const EncArgs& a)
                     C.lane = opaque_lane(threadIdx.x & 63);
                     C.f = f + fr;
                     C.P = a.params + C.f;
-                    C.T = (const LdsTables*)((const uint8_t*)T + sT * fr);
-                    C.Sl = (const ZwSegment*)((const uint8_t*)Sl + sS * fr);
-                    C.top_y = top_y + TS.y * fr;
-                    C.top_u = top_u + TS.u * fr;
-                    C.top_v = top_v + TS.v * fr;
-                    C.top_c = top_c + TS.c * fr;
-                    C.top_derr = top_derr + TS.d * fr;
+                    C.T = (const LdsTables*)((const uint8_t*)T + L.sT * fr);
+                    C.Sl = (const ZwSegment*)((const uint8_t*)Sl + L.sS * fr);
+                    C.top_y = top_y + L.sy * fr;
+                    C.top_u = top_u + L.su * fr;
+                    C.top_v = top_v + L.sv * fr;
+                    C.top_c = top_c + L.sc * fr;
+                    C.top_derr = top_derr + L.sd * fr;
                     C.M = fr ? Mp[1] : Mp[0];
                     C.method = fr ? meth1 : meth0;
                     C.mbx = mbx;
@@ -3614,19 +3353,7 @@ __device__ __forceinline__ void encode_body(const EncArgs& a)
                 };
                 auto pst = [&](int fr, int k) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)W->pst[fr][k]); };
                 wait_above(min(mbx + 1, mbw));
-#if ZW_DYN_PRIO > 0
-                {
-                    int slack = mbw;
-                    if (mby > 0) {
-                        const int v = __builtin_amdgcn_readfirstlane(
-                            __hip_atomic_load(&progress[prevw], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-                        if ((v >> 16) == mby - 1) slack = (v & 0xffff) - mbx - 1;
-                    }
-                    constexpr int dp = PASS == 1 ? ZW_DYN_PRIO1 : ZW_DYN_PRIO;
-                    const int pr_ = slack >= dp * 3 ? 3 : (slack >= dp * 2 ? 2 : (slack >= dp ? 1 : 0));
-                    set_prio(PASS == 1 ? min(pr_, ZW_P1_LUMA_MAX) : pr_);
-                }
-#endif
+                luma_issue_prio<PASS>(progress, prevw, mbx, mby, mbw);
                 PH_MARK(0);
 ZW_PAIR_LOOP
                 for (int fr = 0; fr < 2; fr++) {
@@ -3636,7 +3363,7 @@ ZW_PAIR_LOOP
                     }
                     enter(fr);
                     const MbFetch fm = fetch_mb(&a, C.f, lane, mbx, mby);
-                    setup_ctx(C, &a, seg_lut + 256 * fr, W, mbx, mby, fm);
+                    setup_ctx(C, &a, seg_lut + L.sL * fr, W, mbx, mby, fm);
                     build_luma_border(C, 0);
                     int l_;
                     unsigned long long s_;
@@ -3666,11 +3393,11 @@ ZW_PAIR_LOOP
                     Ctx CA = C, CB = C;
                     CA.lane = CB.lane = opaque_lane(threadIdx.x & 63);
                     CA.T = T;
-                    CB.T = (const LdsTables*)((const uint8_t*)T + sT);
+                    CB.T = (const LdsTables*)((const uint8_t*)T + L.sT);
                     CA.M = Mp[0];
                     CB.M = Mp[1];
                     CA.S = Sl + (s0 >> 8);
-                    CB.S = (const ZwSegment*)((const uint8_t*)Sl + sS) + (s1 >> 8);
+                    CB.S = (const ZwSegment*)((const uint8_t*)Sl + L.sS) + (s1 >> 8);
                     CA.sY = Mp[0]->sy;
                     CB.sY = Mp[1]->sy;
                     const unsigned long long i0 = pst(0, 1) | ((unsigned long long)pst(0, 2) << 32);
@@ -3729,17 +3456,11 @@ ZW_PAIR_LOOP
     uint8_t* const gtd = ROWS ? rb + RL.td : nullptr;
     for (int it = 0, yk = rw;; it++) {
         const int mby = ROWS ? row_ticket(&rsync[0]) : (skip_mode ? yk : rw + it * nrw);
-        if (skip_mode) yk = next_row(yk);
+        if (skip_mode) yk = RS::next_row(wv, yk, mbh);
         if (mby >= mbh) break;
-        if (lane < 20) C.M->left_y[lane] = 129;
-        if (lane < 12) {
-            C.M->left_u[lane] = 129;
-            C.M->left_v[lane] = 129;
-            C.M->left_c[lane] = 0;
-        }
-        if (lane < 4) C.M->left_derr[lane] = 0;
+        row_start(C.M, lane);
         wsync();
-        const int prevw = (!ROWS && mby > 0) ? wave_of_row(mby - 1) : 0;
+        const int prevw = (!ROWS && mby > 0) ? RS::wave_of_row(mby - 1) : 0;
         int seen = -1;  // ROWS: last progress value read of the row above
         int* const prog_above = ROWS ? rsync + 4 + (mby > 0 ? mby - 1 : 0) : nullptr;
         // the row above has finished `need` MBs
@@ -3748,16 +3469,7 @@ ZW_PAIR_LOOP
             if (ROWS) row_wait(prog_above, need, rerr, seen);
             else wait_row(progress, prevw, (mby - 1) * 65536 + need);
         };
-#ifndef ZW_FETCH_AHEAD
-#define ZW_FETCH_AHEAD (PASS == 2)
-#endif
-        // Pass 1 loads the MB's source words and alpha at the top of its
-        // iteration, in flight during the wait for the row above; pass 2 fetches
-        // them one MB ahead.  (Fetched ahead, the words do not stay in registers:
-        // each is spilled to scratch right after its load, so the three loads
-        // run one after another, each also waiting for the previous MB's stores
-        // -- vmcnt counts stores.  Measured per 256 1080p frames: pass 1 29.12 ->
-        // 28.98 ms loading at the top, pass 2 37.38 -> 37.64 ms.)
+        // (pass 2 fetches the MB's words one MB ahead: see ZW_FETCH_AHEAD)
         MbFetch nx;
         if (ZW_FETCH_AHEAD) nx = fetch_mb(&a, f, lane, 0, mby);
         for (int mbx = 0; mbx < mbw; mbx++) {
@@ -3802,25 +3514,7 @@ ZW_PAIR_LOOP
                 C.ocx = mbx * 12;
                 C.od = mbx * 4;
             }
-#if ZW_DYN_PRIO > 0
-            if (!ROWS) {
-                // Issue priority from the slack to the row above.  VALU issue is
-                // arbitrated by priority, then wave age: at equal priority the
-                // youngest waves of each SIMD run slowest and every row behind
-                // theirs waits on them (35 % of the oldest waves' time).  A row
-                // that trails the row above by more than the two-MB minimum is
-                // the one later rows wait for, so it issues first.
-                int slack = mbw;
-                if (mby > 0) {
-                    const int v = __builtin_amdgcn_readfirstlane(
-                        __hip_atomic_load(&progress[prevw], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-                    if ((v >> 16) == mby - 1) slack = (v & 0xffff) - mbx - 1;
-                }
-                constexpr int dp = PASS == 1 ? ZW_DYN_PRIO1 : ZW_DYN_PRIO;
-                const int p = slack >= dp * 3 ? 3 : (slack >= dp * 2 ? 2 : (slack >= dp ? 1 : 0));
-                set_prio(PASS == 1 ? min(p, ZW_P1_LUMA_MAX) : p);
-            }
-#endif
+            if (!ROWS) luma_issue_prio<PASS>(progress, prevw, mbx, mby, mbw);
             PH_MARK(0);
             setup_ctx(C, &a, seg_lut, W, mbx, mby, cur);
             build_luma_border(C, 0);
@@ -3989,16 +3683,7 @@ extern "C" hipError_t zwk_quant_blocks(hipStream_t s, const int* coeffs, const u
 
 static size_t encode_lds_bytes(int mbw, int nw, bool rows, int pass, int fp = 1)
 {
-    size_t off = 0;
-    off += ((sizeof(LdsTables) + 15) & ~(size_t)15) * fp;
-    off += ((4 * sizeof(ZwSegment) + 15) & ~(size_t)15) * fp;
-    off += 256 * fp;
-    off += ((sizeof(WaveLds) + 15) & ~(size_t)15) * nw;
-    if (fp == 2) off += ((sizeof(MbLds) + 15) & ~(size_t)15) * nw;
-    off += 64;
-    off += 256;
-    const TopLds t(mbw, rows, pass);
-    return off + (t.y + t.u + t.v + t.c + t.d) * fp;
+    return EncLds(mbw, rows, pass).bytes(nw, fp);
 }
 
 // Frame pairs (k_encode_pass1_fp / k_encode_pass2_fp) for launches of at
@@ -4054,15 +3739,8 @@ extern "C" hipError_t zwk_analysis(hipStream_t s, const uint8_t* Y, const uint8_
                                    int mbh, size_t ysz, size_t csz, uint8_t* alpha, uint32_t* histo, int nframes)
 {
     const int nmb = mbw * mbh;
-#ifndef ZW_AN_FORM
-#define ZW_AN_FORM 4  // 4: k_analysis4 (four MBs a wave); 1: k_analysis (one MB a wave)
-#endif
-    if (ZW_AN_FORM == 4)
-        hipLaunchKernelGGL(k_analysis4, dim3((nmb + 16 * ZW_AN4_GPW - 1) / (16 * ZW_AN4_GPW), nframes), dim3(256), 0, s, Y,
-                           U, V, mbw, mbh, ysz, csz, alpha, histo);
-    else
-        hipLaunchKernelGGL(k_analysis, dim3((nmb + 4 * ZW_AN_MPW - 1) / (4 * ZW_AN_MPW), nframes), dim3(256), 0, s, Y, U,
-                           V, mbw, mbh, ysz, csz, alpha, histo);
+    hipLaunchKernelGGL(k_analysis4, dim3((nmb + 16 * ZW_AN4_GPW - 1) / (16 * ZW_AN4_GPW), nframes), dim3(256), 0, s, Y, U,
+                       V, mbw, mbh, ysz, csz, alpha, histo);
     return hipGetLastError();
 }
 

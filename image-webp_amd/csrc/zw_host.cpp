@@ -441,7 +441,7 @@ static int device_cus(int device)
 // encode_frame_lossy's dimension rule (vp8.rs:3143-3148): any u16, the header
 // keeping the low 14 bits (vp8.rs:326-327; zwh::emit_frame does the same).
 // Zero is refused (the reference has no meaningful zero-MB frame).  Frames
-// wider than the batch kernels' LDS takes (zwk_encode_max_mbw(0), 1 568 MBs)
+// wider than the batch kernels' LDS takes (zwk_encode_max_mbw(0), 1 560 MBs)
 // run the row-parallel kernels, whose LDS holds any u16 width.
 static bool encode_dims_ok(uint32_t width, uint32_t height)
 {

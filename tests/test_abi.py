@@ -59,6 +59,16 @@ def test_no_cpu_fallback_without_device(lib):
     assert e.value.code == 4
 
 
+def test_encode_lds_layout_widths(lib):
+    """The widest frame (in MBs) the encode kernels' LDS layout holds: the batch
+    shapes (every row array of the frame in LDS) and the row-parallel shapes
+    (any u16 width).  The kernels carve and the host sizes the launches from
+    one layout (EncLds, zw_enc_kernels.hip); these are its values, no device
+    needed."""
+    assert lib.zwk_encode_max_mbw(0) == 1560
+    assert lib.zwk_encode_max_mbw(1) == 4096
+
+
 def test_strerror(lib):
     import zwebp
     L = zwebp.load_library()

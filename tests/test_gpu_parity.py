@@ -280,6 +280,53 @@ def test_encode_frame_pairs_methods(ctx, monkeypatch, m, q):
         assert outs[i] == ref, f"frame {i}"
 
 
+_FRAME_PAIRS_CHILD = r"""
+import os, sys
+sys.path[:0] = [os.path.join(sys.argv[1], "image-webp_amd"), os.path.join(sys.argv[1], "tests")]
+import oracle_lib as O
+import zwebp
+from zwebp.synth import synth_rgba
+w, h, n = (int(v) for v in sys.argv[2:5])
+imgs = [synth_rgba(w, h, 0x5EED5000 + 16 * w + i, ("natural", "noise", "flat")[i % 3]) for i in range(n)]
+ctx = zwebp.Context(0)
+outs = zwebp.encode_batch(imgs, w, h, zwebp.ColorType.Rgba8, 75, 4, ctx=ctx)
+for i, im in enumerate(imgs):
+    rc, ref, _ = O.encode(im, w, h, 3, 75, 4)
+    assert rc == 0 and outs[i] == ref, f"frame {i}"
+ctx.close()
+print("ok")
+"""
+
+
+@pytest.mark.parametrize("w,h,n", [(32, 224, 3), (16, 16, 2)])
+def test_encode_frame_pairs_rounds_and_single_mb(w, h, n):
+    """Both passes in frame pairs, forced on (a fresh process: ZW_ENC_FP is read
+    once).  2 x 14 MBs, three frames: fourteen rows exceed the 12 waves of pass 2
+    and the 10 luma waves of pair pass 1, so a wave's second round and its wait
+    on a row it does not own run in the pair loop, and the odd count leaves a
+    one-frame workgroup.  16 x 16, two frames: one MB per frame, no row above
+    and no right neighbour.  Every frame equals the reference's stream."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, ZW_ENC_FP="1", ZW_ENC_ROWS="0")
+    r = subprocess.run([sys.executable, "-c", _FRAME_PAIRS_CHILD, root, str(w), str(h), str(n)], env=env,
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "ok" in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
+
+
+def test_encode_batch_kernels_three_rounds(ctx, monkeypatch):
+    """The batch kernels on one 2 x 26 MB frame: the rows span three rounds of
+    pass 1's skip-mode schedule and of pass 2's round-robin, and at two MBs a
+    row every wait is on the last MB of the row above."""
+    monkeypatch.setenv("ZW_ENC_ROWS", "0")
+    w, h = 32, 416
+    img = synth_rgba(w, h, 0x5EED6000, "natural")
+    out = zwebp.encode_frame_lossy(img, w, h, zwebp.ColorType.Rgba8, 75, 4, ctx=ctx)
+    rc, ref, _ = O.encode(img, w, h, 3, 75, 4)
+    assert rc == 0 and out == ref
+
+
 def test_encode_repeat_streaming(ctx, monkeypatch):
     """encode_repeat: batch k+1's pass 1 overlaps batch k's emission (separate
     pass-1 / pass-2 pack buffers); several chunks per lane; every batch's
@@ -318,7 +365,7 @@ def test_encode_api_errors(ctx):
 def test_encode_beyond_14bit_dims(ctx, w, h):
     """encode_frame_lossy accepts any u16 dimension (vp8.rs:3143-3148) and the
     header keeps the low 14 bits (vp8.rs:326-327): the product's bytes equal the
-    oracle's up to the widest frame whose LDS rows fit a CU (1568 MBs)."""
+    oracle's up to the widest frame whose LDS rows fit a CU (1560 MBs)."""
     img = np.ascontiguousarray(synth_rgba(w, h, 0x5EED2000 + w)[..., :3])
     rc, ref, _ = O.encode(img, w, h, 2, 75, 4)
     assert rc == 0
@@ -330,7 +377,7 @@ def test_encode_beyond_14bit_dims(ctx, w, h):
 @pytest.mark.parametrize("w,h", [(25089, 1), (25600, 16), (65535, 16), (40000, 33)])
 def test_encode_wide_frames(ctx, w, h):
     """encode_frame_lossy takes any u16 width (vp8.rs:3143-3148).  Frames wider
-    than the batch kernels' LDS holds (1 568 MBs) run the row-parallel kernels,
+    than the batch kernels' LDS holds (1 560 MBs) run the row-parallel kernels,
     whose LDS no longer grows with the width: the bitstream equals the oracle's
     (the header keeps the low 14 bits of the width, vp8.rs:326-327).  A width of
     65 536 is not a u16: InvalidDimensions, as the reference's try_into."""
