@@ -111,3 +111,11 @@ struct ZwFilterParams {
     int32_t mbw, mbh, pad;
     uint8_t level[4][2], ilimit[4][2], hev[4][2], pad2[8];
 };
+
+// Where k_yuv2rgb_dev writes (zw_device_images, include/zwebp.h): strides in
+// elements from the chunk's first frame, and the float dtypes' per-channel
+// scale and bias.
+struct ZwY2rDev {
+    size_t frame_stride, plane_stride, row_stride;
+    float scale[4], bias[4];
+};

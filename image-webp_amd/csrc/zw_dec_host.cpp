@@ -1,7 +1,8 @@
 // zw_dec_host.cpp -- VP8 keyframe decoder, device side: the chunk pipeline that
 // feeds the host parser's packed MB records (zw_dec_parse.cpp) or the device
 // token parse's (zw_dec_tokens.hip) to the reconstruction / loop filter kernels
-// and brings the planes or packed RGB(A) back.
+// and brings the planes or packed RGB(A) back, or converts them straight into
+// the caller's device memory (zw_vp8_decode_batch_device).
 //
 //   host  : zw_dec_parse.cpp (headers, modes, tokens -> one packed record per
 //           macroblock; no device code there).
@@ -29,6 +30,9 @@ hipError_t zwk_dec_recon(hipStream_t s, const uint8_t* recs, const uint32_t* mof
                          size_t ysz, size_t csz, int nframes, uint8_t* tiles);
 hipError_t zwk_yuv2rgb(hipStream_t s, const uint8_t* Y, const uint8_t* U, const uint8_t* V, size_t ysz, size_t csz,
                        int w, int h, int ys, int cs, int bpp, int fancy, uint8_t* out, int nframes);
+hipError_t zwk_yuv2rgb_dev(hipStream_t s, const uint8_t* Y, const uint8_t* U, const uint8_t* V, size_t ysz, size_t csz,
+                           int w, int h, int ys, int cs, int layout, int dtype, int channels, int fancy, void* out,
+                           const ZwY2rDev* P, int nframes);
 hipError_t zwk_dec_rows(hipStream_t s, int phase, const uint8_t* recs, const uint32_t* moff, const uint64_t* fbase,
                         const void* quant, uint8_t* Y, uint8_t* U, uint8_t* V, uint8_t* flags, const ZwFilterParams* fp,
                         int mbw, int mbh, size_t ysz, size_t csz, int nframes, int* rowsync, uint8_t* borders, int rows);
@@ -506,7 +510,8 @@ struct DecSink {
     virtual int enqueue(zw_ctx* ctx, DecChunk& C) = 0;
     // the set's event that marks the chunk's device work done
     virtual DecEv wait_event() const = 0;
-    // pinned download staging per frame
+    // pinned download staging per frame; 0: the frames stay on the device, and
+    // the chunk has nothing to bring down (copy_down / place are not called)
     virtual size_t staging_per_frame(const DecChunk& C) const = 0;
     // the chunk's frames [a, b) from the device into the staging `hout`
     virtual int copy_down(zw_ctx* ctx, const DecChunk& C, uint8_t* hout, int a, int b) = 0;
@@ -867,26 +872,29 @@ struct DecRun {
 
     // Waits for the chunk's device work, checks the kernels' error words, then
     // brings the frames down through pinned staging and fans them out to the
-    // caller.  The download and fan-out times are added before the download's
+    // caller (nothing for a sink without host staging).  The download and fan-out times are added before the download's
     // status is looked at: they are wall time spent either way.
     int finish_chunk(DecChunk& C)
     {
         const DecMeta& M = C.meta;
-        uint8_t* hout = (uint8_t*)ctx->pin[PIN_DOWNLOAD].reserve((size_t)M.n * sink.staging_per_frame(C));
-        if (!hout) return ZW_ENOMEM;
+        const size_t staging = (size_t)M.n * sink.staging_per_frame(C);
+        uint8_t* hout = staging ? (uint8_t*)ctx->pin[PIN_DOWNLOAD].reserve(staging) : nullptr;
+        if (staging && !hout) return ZW_ENOMEM;
         HIPOK(hipEventSynchronize(C.set->ev[sink.wait_event()]));
         if (int r = tokens_error(ctx, C.src.err, M.n)) return r;
         if (int r = rows_error(ctx, C.d_rs, M.n, M.mbh)) return r;
-        const double tf = dec_now_ms();
-        std::vector<int> oom(M.n, 0);
-        double dl_ms = 0;
-        const int dr = dec_download_fan(ctx, K, sink, C, hout, oom, &dl_ms);
-        ctx->dec_host_ms[1] += dl_ms;
-        ctx->dec_host_ms[2] += dec_now_ms() - tf;
-        if (K.timing) fprintf(stderr, "[dec] download+fanout %.2f ms\n", dec_now_ms() - tf);
-        if (dr) return dr;
-        for (int i = 0; i < M.n; i++)
-            if (oom[i]) return ZW_ENOMEM;
+        if (staging) {  // (a sink that keeps the frames on the device: no download, no fan-out)
+            const double tf = dec_now_ms();
+            std::vector<int> oom(M.n, 0);
+            double dl_ms = 0;
+            const int dr = dec_download_fan(ctx, K, sink, C, hout, oom, &dl_ms);
+            ctx->dec_host_ms[1] += dl_ms;
+            ctx->dec_host_ms[2] += dec_now_ms() - tf;
+            if (K.timing) fprintf(stderr, "[dec] download+fanout %.2f ms\n", dec_now_ms() - tf);
+            if (dr) return dr;
+            for (int i = 0; i < M.n; i++)
+                if (oom[i]) return ZW_ENOMEM;
+        }
         float ms = 0.f;
         if (sink.wait_event() == DEC_EV_CALLER &&
             hipEventElapsedTime(&ms, C.set->ev[DEC_EV_FILTER_DONE], C.set->ev[DEC_EV_CALLER]) == hipSuccess)
@@ -1185,6 +1193,113 @@ extern "C" int zw_vp8_decode_rgb_batch_into(zw_ctx* ctx, int n, const uint8_t* c
         return dec_rgb_batch(ctx, i1 - i0, data + i0, lens + i0, bpp, upsampling, nullptr, outs + i0, out_lens + i0,
                              stride_bytes, widths ? widths + i0 : nullptr, heights ? heights + i0 : nullptr);
     });
+}
+
+namespace {
+
+// zw_vp8_decode_batch_device's output: k_yuv2rgb_dev after the filter, from the
+// planes straight into the caller's device memory.  Nothing comes down.
+struct DeviceSink : DecSink {
+    size_t w = 0, h = 0, elsize = 0;
+    int layout = 0, dtype = 0, channels = 0, fancy = 0;
+    uint8_t* data = nullptr;
+    ZwY2rDev P = {};
+    size_t extra_per_frame() const override { return 0; }
+    int enqueue(zw_ctx* ctx, DecChunk& C) override
+    {
+        const DecMeta& M = C.meta;
+        for (int i = 0; i < M.n; i++)
+            if ((size_t)M.F[i].width != w || (size_t)M.F[i].height != h) return ZW_EINVAL;
+        hipStream_t s = ctx_stream(ctx);
+        HIPOK(zwk_yuv2rgb_dev(s, C.d + C.lay.y, C.d + C.lay.u, C.d + C.lay.v, M.ysz, M.csz, (int)w, (int)h, M.mbw * 16,
+                              M.mbw * 8, layout, dtype, channels, fancy,
+                              data + (size_t)C.first * P.frame_stride * elsize, &P, M.n));
+        HIPOK(hipEventRecord(C.set->ev[DEC_EV_CALLER], s));
+        return ZW_OK;
+    }
+    DecEv wait_event() const override { return DEC_EV_CALLER; }
+    size_t staging_per_frame(const DecChunk&) const override { return 0; }
+    int copy_down(zw_ctx*, const DecChunk&, uint8_t*, int, int) override { return ZW_OK; }
+    bool place(const DecChunk&, const uint8_t*, int) override { return true; }
+};
+
+// a + b * c in size_t; false on overflow
+static bool madd(size_t a, size_t b, size_t c, size_t* out)
+{
+    size_t t;
+    return !__builtin_mul_overflow(b, c, &t) && !__builtin_add_overflow(a, t, out);
+}
+
+}  // namespace
+
+extern "C" int zw_vp8_decode_batch_device(zw_ctx* ctx, int n, const uint8_t* const* data, const size_t* lens,
+                                          const zw_device_images* out, uint32_t* width, uint32_t* height)
+{
+    if (!ctx || n <= 0 || !data || !lens || !out || !out->data) return ZW_EINVAL;
+    if ((out->layout != ZW_LAYOUT_HWC && out->layout != ZW_LAYOUT_CHW) ||
+        (out->dtype != ZW_DTYPE_U8 && out->dtype != ZW_DTYPE_F16 && out->dtype != ZW_DTYPE_F32) ||
+        (out->channels != 3 && out->channels != 4) ||
+        (out->upsampling != ZW_UPSAMPLE_BILINEAR && out->upsampling != ZW_UPSAMPLE_SIMPLE))
+        return ZW_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (!data[i] && lens[i]) return ZW_EINVAL;
+    DeviceSink sink;
+    {  // dimensions first (they bound what the kernel addresses)
+        DecFrame f0;
+        const int r = parse_header(f0, data[0], lens[0]);
+        if (r) return r;
+        sink.w = f0.width;
+        sink.h = f0.height;
+    }
+    const size_t w = sink.w, h = sink.h, ch = (size_t)out->channels, N = (size_t)n;
+    if (w == 0 || h == 0) return ZW_EINVALID_DIMENSIONS;
+    for (int i = 1; i < n; i++) {  // one size per batch (a frame too short for dimensions reports its own error)
+        int wi = 0, hi = 0;
+        if (peek_dims(data[i], lens[i], &wi, &hi) && ((size_t)wi != w || (size_t)hi != h)) return ZW_EINVAL;
+    }
+    // the elements one frame spans, then the last element the batch addresses
+    const bool chw = out->layout == ZW_LAYOUT_CHW;
+    size_t span = 0, last = 0;
+    if (chw) {
+        size_t plane = 0;
+        if (out->row_stride < w || !madd(w, h - 1, out->row_stride, &plane) || out->plane_stride < plane ||
+            !madd(plane, ch - 1, out->plane_stride, &span))
+            return ZW_EINVAL;
+    } else {
+        size_t row = 0;
+        if (!madd(0, w, ch, &row) || out->row_stride < row || !madd(row, h - 1, out->row_stride, &span)) return ZW_EINVAL;
+    }
+    if (n > 1 && out->frame_stride < span) return ZW_EINVAL;  // frames must not overlap
+    if (!madd(span, N - 1, out->frame_stride, &last) || out->capacity < last) return ZW_EINVAL;
+    sink.elsize = out->dtype == ZW_DTYPE_U8 ? 1 : (out->dtype == ZW_DTYPE_F16 ? 2 : 4);
+    {  // device memory on the context's device, whole elements
+        size_t bytes = 0;
+        if (!madd(0, out->capacity, sink.elsize, &bytes) || ((uintptr_t)out->data & (sink.elsize - 1))) return ZW_EINVAL;
+        HIPOK(hipSetDevice(ctx->device));
+        hipPointerAttribute_t at;
+        memset(&at, 0, sizeof at);
+        if (hipPointerGetAttributes(&at, out->data) != hipSuccess) {
+            (void)hipGetLastError();  // (an unregistered host pointer)
+            return ZW_EINVAL;
+        }
+        if (at.type != hipMemoryTypeDevice || at.device != ctx->device) return ZW_EINVAL;
+    }
+    sink.layout = out->layout;
+    sink.dtype = out->dtype;
+    sink.channels = out->channels;
+    sink.fancy = out->upsampling == ZW_UPSAMPLE_BILINEAR;
+    sink.data = (uint8_t*)out->data;
+    sink.P.frame_stride = out->frame_stride;
+    sink.P.plane_stride = out->plane_stride;
+    sink.P.row_stride = out->row_stride;
+    for (int c = 0; c < 4; c++) {
+        sink.P.scale[c] = out->scale[c];
+        sink.P.bias[c] = out->bias[c];
+    }
+    if (int r = DecRun(ctx, n, data, lens, sink).run()) return r;
+    if (width) *width = (uint32_t)w;
+    if (height) *height = (uint32_t)h;
+    return ZW_OK;
 }
 
 extern "C" int zw_vp8_decode_rgb(zw_ctx* ctx, const uint8_t* vp8, size_t len, int bpp, int upsampling, zw_bytes* out,

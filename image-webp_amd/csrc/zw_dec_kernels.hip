@@ -1183,6 +1183,81 @@ __device__ __forceinline__ uint32_t yuv2rgb_px(const uint8_t* Y, const uint8_t* 
 #ifndef ZW_Y2R_NOCOMP
 #define ZW_Y2R_NOCOMP 0  // calibration: the same loads and stores, pixels not computed
 #endif
+// The device functions k_yuv2rgb and k_yuv2rgb_dev share.  y2r_cols: the six
+// local chroma columns x/2-1 .. x/2+4 of one plane row q from its three aligned
+// words at columns c0, c1, c2 (lok / rok: the left / right neighbour word
+// exists; otherwise the edge byte stands in for it).
+__device__ __forceinline__ void y2r_cols(const uint8_t* q, int c0, int c1, int c2, bool lok, bool rok, int* c6)
+{
+    const uint32_t a = *(const uint32_t*)(q + c0), m = *(const uint32_t*)(q + c1), z = *(const uint32_t*)(q + c2);
+    c6[0] = (int)(lok ? a >> 24 : m & 255u);
+    c6[5] = (int)(rok ? z & 255u : m >> 24);
+#pragma unroll
+    for (int k = 1; k < 5; k++) c6[k] = (int)((m >> (8 * (k - 1))) & 255u);
+}
+
+// y2r_row8: 8 pixels of one row from its Y bytes and the six chroma columns of
+// its main (M) and secondary (S) chroma rows, as R | G << 8 | B << 16 | 255 << 24.
+// (Left to the inliner, which inlines it everywhere: forced inlining runs
+// earlier and schedules k_yuv2rgb differently from the lambda this was.)
+template <bool FANCY>
+__device__ inline void y2r_row8(uint2 yy, const int* uM, const int* uS, const int* vM, const int* vS, uint32_t* px)
+{
+    // fancy: 9 m + 3 s1 + 3 s2 + t = 3 (3 m + s)[mc] + (3 m + s)[sc] per column pair
+    int tu[6], tv[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        tu[k] = FANCY ? 3 * uM[k] + uS[k] : uM[k];
+        tv[k] = FANCY ? 3 * vM[k] + vS[k] : vM[k];
+    }
+    int uu[8], vv[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const int jm = 1 + (i >> 1);  // local chroma column of pixel x + i
+        if (FANCY) {
+            const int js = (i & 1) ? jm + 1 : jm - 1;
+            uu[i] = (3 * tu[jm] + tu[js] + 8) >> 4;
+            vv[i] = (3 * tv[jm] + tv[js] + 8) >> 4;
+        } else {
+            uu[i] = tu[jm];
+            vv[i] = tv[jm];
+        }
+    }
+#if ZW_Y2R_PK
+#pragma unroll
+    for (int i = 0; i < 8; i += 2) {
+        const uint32_t yw = i < 4 ? yy.x : yy.y;
+        const uint32_t y2 = __builtin_amdgcn_perm(0u, yw, (i & 2) ? 0x0c030c02u : 0x0c010c00u);
+        yuv_px2(__builtin_bit_cast(zh2, y2), __builtin_bit_cast(zh2, pack_lo(uu[i], uu[i + 1])),
+                __builtin_bit_cast(zh2, pack_lo(vv[i], vv[i + 1])), px[i], px[i + 1]);
+    }
+#else
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+        px[i] = yuv_px((int)(((i < 4 ? yy.x : yy.y) >> (8 * (i & 3))) & 255u), uu[i], vv[i]);
+#endif
+}
+
+// y2r_store8: the 8 pixels of a row packed 4 or 3 bytes apiece, as two 16-byte
+// nontemporal stores or six 4-byte stores (o aligned to 16 / 4).
+template <int BPP>
+__device__ __forceinline__ void y2r_store8(uint8_t* o, const uint32_t* px)
+{
+    if (BPP == 4) {
+        __builtin_nontemporal_store(zu4{px[0], px[1], px[2], px[3]}, (zu4*)o);
+        __builtin_nontemporal_store(zu4{px[4], px[5], px[6], px[7]}, (zu4*)o + 1);
+    } else {
+        uint32_t* d = (uint32_t*)o;
+#pragma unroll
+        for (int g = 0; g < 2; g++) {
+            const uint32_t p0 = px[4 * g], p1 = px[4 * g + 1], p2 = px[4 * g + 2], p3 = px[4 * g + 3];
+            d[3 * g + 0] = (p0 & 0xffffffu) | (p1 << 24);
+            d[3 * g + 1] = ((p1 >> 8) & 0xffffu) | (p2 << 16);
+            d[3 * g + 2] = ((p2 >> 16) & 0xffu) | ((p3 & 0xffffffu) << 8);
+        }
+    }
+}
+
 template <int BPP, bool FANCY>
 __global__ __launch_bounds__(256) void k_yuv2rgb(const uint8_t* __restrict__ Y, const uint8_t* __restrict__ U,
                                                  const uint8_t* __restrict__ V, size_t ysz, size_t csz, int w, int h,
@@ -1207,12 +1282,7 @@ __global__ __launch_bounds__(256) void k_yuv2rgb(const uint8_t* __restrict__ Y, 
         const int c1 = x >> 1, c0 = lok ? c1 - 4 : c1, c2 = rok ? c1 + 4 : c1;
         // the six local chroma columns x/2-1 .. x/2+4 of one plane row
         auto cols = [&](const uint8_t* P, int rr, int* c6) {
-            const uint8_t* q = P + (size_t)rr * cs;
-            const uint32_t a = *(const uint32_t*)(q + c0), m = *(const uint32_t*)(q + c1), z = *(const uint32_t*)(q + c2);
-            c6[0] = (int)(lok ? a >> 24 : m & 255u);
-            c6[5] = (int)(rok ? z & 255u : m >> 24);
-#pragma unroll
-            for (int k = 1; k < 5; k++) c6[k] = (int)((m >> (8 * (k - 1))) & 255u);
+            y2r_cols(P + (size_t)rr * cs, c0, c1, c2, lok, rok, c6);
         };
         // chroma rows j0-1 .. j0+RP-1 (clamped): pair j0+p blends rows p (main of its
         // upper row 2j-1) and p+1 (main of its lower row 2j)
@@ -1223,56 +1293,7 @@ __global__ __launch_bounds__(256) void k_yuv2rgb(const uint8_t* __restrict__ Y, 
             cols(U, cr, uc[i]);
             cols(V, cr, vc[i]);
         }
-        auto row8 = [&](uint2 yy, const int* uM, const int* uS, const int* vM, const int* vS, uint32_t* px) {
-            // fancy: 9 m + 3 s1 + 3 s2 + t = 3 (3 m + s)[mc] + (3 m + s)[sc] per column pair
-            int tu[6], tv[6];
-#pragma unroll
-            for (int k = 0; k < 6; k++) {
-                tu[k] = FANCY ? 3 * uM[k] + uS[k] : uM[k];
-                tv[k] = FANCY ? 3 * vM[k] + vS[k] : vM[k];
-            }
-            int uu[8], vv[8];
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-                const int jm = 1 + (i >> 1);  // local chroma column of pixel x + i
-                if (FANCY) {
-                    const int js = (i & 1) ? jm + 1 : jm - 1;
-                    uu[i] = (3 * tu[jm] + tu[js] + 8) >> 4;
-                    vv[i] = (3 * tv[jm] + tv[js] + 8) >> 4;
-                } else {
-                    uu[i] = tu[jm];
-                    vv[i] = tv[jm];
-                }
-            }
-#if ZW_Y2R_PK
-#pragma unroll
-            for (int i = 0; i < 8; i += 2) {
-                const uint32_t yw = i < 4 ? yy.x : yy.y;
-                const uint32_t y2 = __builtin_amdgcn_perm(0u, yw, (i & 2) ? 0x0c030c02u : 0x0c010c00u);
-                yuv_px2(__builtin_bit_cast(zh2, y2), __builtin_bit_cast(zh2, pack_lo(uu[i], uu[i + 1])),
-                        __builtin_bit_cast(zh2, pack_lo(vv[i], vv[i + 1])), px[i], px[i + 1]);
-            }
-#else
-#pragma unroll
-            for (int i = 0; i < 8; i++)
-                px[i] = yuv_px((int)(((i < 4 ? yy.x : yy.y) >> (8 * (i & 3))) & 255u), uu[i], vv[i]);
-#endif
-        };
-        auto store8 = [&](uint8_t* o, const uint32_t* px) {
-            if (BPP == 4) {
-                __builtin_nontemporal_store(zu4{px[0], px[1], px[2], px[3]}, (zu4*)o);
-                __builtin_nontemporal_store(zu4{px[4], px[5], px[6], px[7]}, (zu4*)o + 1);
-            } else {
-                uint32_t* d = (uint32_t*)o;
-#pragma unroll
-                for (int g = 0; g < 2; g++) {
-                    const uint32_t p0 = px[4 * g], p1 = px[4 * g + 1], p2 = px[4 * g + 2], p3 = px[4 * g + 3];
-                    d[3 * g + 0] = (p0 & 0xffffffu) | (p1 << 24);
-                    d[3 * g + 1] = ((p1 >> 8) & 0xffffu) | (p2 << 16);
-                    d[3 * g + 2] = ((p2 >> 16) & 0xffu) | ((p3 & 0xffffffu) << 8);
-                }
-            }
-        };
+        auto store8 = [&](uint8_t* o, const uint32_t* px) { y2r_store8<BPP>(o, px); };
         // the Y words of every row first (all loads in flight before the arithmetic)
         uint2 yw[2 * ZW_Y2R_RP];
 #pragma unroll
@@ -1290,9 +1311,9 @@ __global__ __launch_bounds__(256) void k_yuv2rgb(const uint8_t* __restrict__ Y, 
                 for (int k = 0; k < 8; k++)
                     px[k] = yw[i].x ^ (yw[i].y << k) ^ (uint32_t)(uc[p][k % 6] + vc[p + 1][k % 6]);
             } else if (i & 1) {
-                row8(yw[i], uc[p + 1], uc[p], vc[p + 1], vc[p], px);  // row 2j: main chroma row j
+                y2r_row8<FANCY>(yw[i], uc[p + 1], uc[p], vc[p + 1], vc[p], px);  // row 2j: main chroma row j
             } else {
-                row8(yw[i], uc[p], uc[p + 1], vc[p], vc[p + 1], px);  // row 2j-1: main chroma row j-1
+                y2r_row8<FANCY>(yw[i], uc[p], uc[p + 1], vc[p], vc[p + 1], px);  // row 2j-1: main chroma row j-1
             }
             uint8_t* o = orow(r);
             if (((uintptr_t)o & am) == 0) store8(o, px);
@@ -1328,4 +1349,207 @@ extern "C" hipError_t zwk_yuv2rgb(hipStream_t s, const uint8_t* Y, const uint8_t
         else hipLaunchKernelGGL((k_yuv2rgb<3, false>), grid, dim3(256), 0, s, Y, U, V, ysz, csz, w, h, ys, cs, out);
     }
     return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// k_yuv2rgb_dev: the same pixels as k_yuv2rgb, written straight into the
+// caller's device memory (zw_vp8_decode_batch_device): HWC or CHW, 3 or 4
+// channels, u8 / f16 / f32 elements, strides in elements (ZwY2rDev).  The
+// float dtypes store (float)v * scale[c] + bias[c] as a rounded multiply and a
+// rounded add (no FMA; f16 = that float rounded to nearest even), so a host
+// reproduces them bit for bit.
+//
+// The work split is k_yuv2rgb's (one thread per 8 pixels of a row pair, the
+// chroma loads shared; y2r_cols / y2r_row8 / yuv2rgb_px).  Stores per thread
+// and row: HWC u8 as k_yuv2rgb (y2r_store8); CHW one 8-element vector per
+// plane (8 B u8, 16 B f16, 2 x 16 B f32); HWC floats in 16-byte pieces.  A run
+// whose first element is not aligned for its vector store, and the partial run
+// at the right edge, are stored element by element with the same values.
+// Padding elements (row, plane, frame) are never written.
+// ---------------------------------------------------------------------------
+#ifndef ZW_Y2R_DEV_NT
+#define ZW_Y2R_DEV_NT 1  // nontemporal vector stores, as the RGBA path (the output is written once)
+#endif
+typedef uint32_t zu2 __attribute__((ext_vector_type(2)));
+
+template <class E>
+__device__ __forceinline__ E y2r_elem(uint32_t byte, float scale, float bias)
+{
+    if constexpr (sizeof(E) == 1) return (E)byte;
+    else return (E)__fadd_rn(__fmul_rn((float)byte, scale), bias);  // (float -> _Float16: round to nearest even)
+}
+__device__ __forceinline__ uint32_t y2r_bits(uint8_t v) { return v; }
+__device__ __forceinline__ uint32_t y2r_bits(_Float16 v) { return __builtin_bit_cast(unsigned short, v); }
+__device__ __forceinline__ uint32_t y2r_bits(float v) { return __builtin_bit_cast(uint32_t, v); }
+
+// N consecutive elements (8 or 16 bytes, or a multiple of 16) at o: vector
+// stores when o is aligned for them, else element by element.
+template <class E, int N>
+__device__ __forceinline__ void y2r_store_run(E* o, const E* v)
+{
+    constexpr int EPW = 4 / (int)sizeof(E), NW = N / EPW;
+    static_assert(N % EPW == 0 && (NW == 2 || NW % 4 == 0), "8 bytes or whole 16-byte pieces");
+    constexpr uintptr_t am = NW == 2 ? 7 : 15;
+    if (((uintptr_t)o & am) == 0) {
+        uint32_t wd[NW];
+#pragma unroll
+        for (int i = 0; i < NW; i++) {
+            uint32_t t = 0;
+#pragma unroll
+            for (int k = 0; k < EPW; k++) t |= y2r_bits(v[i * EPW + k]) << (8 * (int)sizeof(E) * k % 32);
+            wd[i] = t;
+        }
+        if constexpr (NW == 2) {
+#if ZW_Y2R_DEV_NT
+            __builtin_nontemporal_store(zu2{wd[0], wd[1]}, (zu2*)o);
+#else
+            *(zu2*)o = zu2{wd[0], wd[1]};
+#endif
+        } else {
+#pragma unroll
+            for (int i = 0; i < NW / 4; i++) {
+                const zu4 q = {wd[4 * i], wd[4 * i + 1], wd[4 * i + 2], wd[4 * i + 3]};
+#if ZW_Y2R_DEV_NT
+                __builtin_nontemporal_store(q, (zu4*)o + i);
+#else
+                ((zu4*)o)[i] = q;
+#endif
+            }
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < N; k++) o[k] = v[k];
+    }
+}
+
+template <int CH, bool FANCY, int LAYOUT, class E>
+__device__ __forceinline__ void y2r_dev_body(const uint8_t* __restrict__ Y, const uint8_t* __restrict__ U,
+                                             const uint8_t* __restrict__ V, size_t ysz, size_t csz, int w, int h,
+                                             int ys, int cs, E* __restrict__ out, const ZwY2rDev& P)
+{
+    const int f = blockIdx.z;
+    const int j0 = (int)blockIdx.y;  // rows 2 j0 - 1 and 2 j0
+    const int x = (int)(blockIdx.x * 256u + threadIdx.x) * 8;
+    if (x >= w) return;
+    Y += (size_t)f * ysz;
+    U += (size_t)f * csz;
+    V += (size_t)f * csz;
+    out += (size_t)f * P.frame_stride;
+    const int cw1 = ((w + 1) >> 1) - 1, ch1 = ((h + 1) >> 1) - 1;
+    auto elem = [&](uint32_t p, int c) { return y2r_elem<E>((p >> (8 * c)) & 255u, P.scale[c], P.bias[c]); };
+    // a full run of row r
+    auto emit8 = [&](int r, const uint32_t* px) {
+        E* o = out + (size_t)r * P.row_stride;
+        if constexpr (LAYOUT == 0 && sizeof(E) == 1) {
+            uint8_t* b = (uint8_t*)o + (size_t)x * CH;
+            if (((uintptr_t)b & (CH == 4 ? 15 : 3)) == 0) y2r_store8<CH>(b, px);
+            else
+                for (int k = 0; k < 8 * CH; k++) b[k] = (uint8_t)(px[k / CH] >> (8 * (k % CH)));
+        } else if constexpr (LAYOUT == 0) {
+            E v[8 * CH];
+#pragma unroll
+            for (int k = 0; k < 8 * CH; k++) v[k] = elem(px[k / CH], k % CH);
+            y2r_store_run<E, 8 * CH>(o + (size_t)x * CH, v);
+        } else {
+#pragma unroll
+            for (int c = 0; c < CH; c++) {
+                E v[8];
+#pragma unroll
+                for (int k = 0; k < 8; k++) v[k] = elem(px[k], c);
+                y2r_store_run<E, 8>(o + (size_t)c * P.plane_stride + (size_t)x, v);
+            }
+        }
+    };
+    const bool fast = x + 8 <= w && (ys & 7) == 0 && (cs & 3) == 0;  // (as k_yuv2rgb)
+    if (fast) {
+        const bool lok = x > 0, rok = (x >> 1) + 4 <= cw1;
+        const int c1 = x >> 1, c0 = lok ? c1 - 4 : c1, c2 = rok ? c1 + 4 : c1;
+        // chroma rows j0-1 and j0 (clamped): main of the upper / the lower row of the pair
+        int uc[2][6], vc[2][6];
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            const int cr = min(max(j0 - 1 + i, 0), ch1);
+            y2r_cols(U + (size_t)cr * cs, c0, c1, c2, lok, rok, uc[i]);
+            y2r_cols(V + (size_t)cr * cs, c0, c1, c2, lok, rok, vc[i]);
+        }
+        uint2 yw[2];
+#pragma unroll
+        for (int i = 0; i < 2; i++) yw[i] = *(const uint2*)(Y + (size_t)min(max(2 * j0 - 1 + i, 0), h - 1) * ys + x);
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            const int r = 2 * j0 - 1 + i;
+            if (r < 0 || r >= h) continue;
+            uint32_t px[8];
+            if (i) y2r_row8<FANCY>(yw[i], uc[1], uc[0], vc[1], vc[0], px);
+            else y2r_row8<FANCY>(yw[i], uc[0], uc[1], vc[0], vc[1], px);
+            emit8(r, px);
+        }
+    } else {
+        const int n = min(8, w - x);
+        for (int i = 0; i < 2; i++) {
+            const int r = 2 * j0 - 1 + i;
+            if (r < 0 || r >= h) continue;
+            E* o = out + (size_t)r * P.row_stride;
+            for (int k = 0; k < n; k++) {
+                const uint32_t p = yuv2rgb_px<FANCY>(Y, U, V, ys, cs, cw1, ch1, r, x + k);
+                for (int c = 0; c < CH; c++) {
+                    if (LAYOUT == 0) o[(size_t)(x + k) * CH + c] = elem(p, c);
+                    else o[(size_t)c * P.plane_stride + (size_t)(x + k)] = elem(p, c);
+                }
+            }
+        }
+    }
+}
+
+// One named kernel per (layout, dtype, channels, upsampling): X(name, CH, FANCY, LAYOUT, E, dtype index)
+#define ZW_Y2R_DEV_KERNELS(X)                                  \
+    X(k_yuv2rgb_dev_hwc_u8_c3_fancy, 3, true, 0, uint8_t, 0)   \
+    X(k_yuv2rgb_dev_hwc_u8_c3_simple, 3, false, 0, uint8_t, 0) \
+    X(k_yuv2rgb_dev_hwc_u8_c4_fancy, 4, true, 0, uint8_t, 0)   \
+    X(k_yuv2rgb_dev_hwc_u8_c4_simple, 4, false, 0, uint8_t, 0) \
+    X(k_yuv2rgb_dev_hwc_f16_c3_fancy, 3, true, 0, _Float16, 1) \
+    X(k_yuv2rgb_dev_hwc_f16_c3_simple, 3, false, 0, _Float16, 1) \
+    X(k_yuv2rgb_dev_hwc_f16_c4_fancy, 4, true, 0, _Float16, 1) \
+    X(k_yuv2rgb_dev_hwc_f16_c4_simple, 4, false, 0, _Float16, 1) \
+    X(k_yuv2rgb_dev_hwc_f32_c3_fancy, 3, true, 0, float, 2)    \
+    X(k_yuv2rgb_dev_hwc_f32_c3_simple, 3, false, 0, float, 2)  \
+    X(k_yuv2rgb_dev_hwc_f32_c4_fancy, 4, true, 0, float, 2)    \
+    X(k_yuv2rgb_dev_hwc_f32_c4_simple, 4, false, 0, float, 2)  \
+    X(k_yuv2rgb_dev_chw_u8_c3_fancy, 3, true, 1, uint8_t, 0)   \
+    X(k_yuv2rgb_dev_chw_u8_c3_simple, 3, false, 1, uint8_t, 0) \
+    X(k_yuv2rgb_dev_chw_u8_c4_fancy, 4, true, 1, uint8_t, 0)   \
+    X(k_yuv2rgb_dev_chw_u8_c4_simple, 4, false, 1, uint8_t, 0) \
+    X(k_yuv2rgb_dev_chw_f16_c3_fancy, 3, true, 1, _Float16, 1) \
+    X(k_yuv2rgb_dev_chw_f16_c3_simple, 3, false, 1, _Float16, 1) \
+    X(k_yuv2rgb_dev_chw_f16_c4_fancy, 4, true, 1, _Float16, 1) \
+    X(k_yuv2rgb_dev_chw_f16_c4_simple, 4, false, 1, _Float16, 1) \
+    X(k_yuv2rgb_dev_chw_f32_c3_fancy, 3, true, 1, float, 2)    \
+    X(k_yuv2rgb_dev_chw_f32_c3_simple, 3, false, 1, float, 2)  \
+    X(k_yuv2rgb_dev_chw_f32_c4_fancy, 4, true, 1, float, 2)    \
+    X(k_yuv2rgb_dev_chw_f32_c4_simple, 4, false, 1, float, 2)
+
+#define ZW_Y2R_DEV_DEFINE(name, CH, FANCY, LAYOUT, E, DT)                                                          \
+    extern "C" __global__ __launch_bounds__(256) void name(                                                        \
+        const uint8_t* __restrict__ Y, const uint8_t* __restrict__ U, const uint8_t* __restrict__ V, size_t ysz,   \
+        size_t csz, int w, int h, int ys, int cs, E* __restrict__ out, ZwY2rDev P)                                 \
+    {                                                                                                              \
+        y2r_dev_body<CH, FANCY, LAYOUT, E>(Y, U, V, ysz, csz, w, h, ys, cs, out, P);                               \
+    }
+ZW_Y2R_DEV_KERNELS(ZW_Y2R_DEV_DEFINE)
+
+// layout 0 HWC / 1 CHW, dtype 0 u8 / 1 f16 / 2 f32, channels 3 / 4 (the host
+// validated them); out = the first frame of the launch.
+extern "C" hipError_t zwk_yuv2rgb_dev(hipStream_t s, const uint8_t* Y, const uint8_t* U, const uint8_t* V, size_t ysz,
+                                      size_t csz, int w, int h, int ys, int cs, int layout, int dtype, int channels,
+                                      int fancy, void* out, const ZwY2rDev* P, int nframes)
+{
+    const void* fn = nullptr;
+#define ZW_Y2R_DEV_PICK(name, CH, FANCY, LAYOUT, E, DT) \
+    if (layout == LAYOUT && dtype == DT && channels == CH && (fancy != 0) == FANCY) fn = (const void*)name;
+    ZW_Y2R_DEV_KERNELS(ZW_Y2R_DEV_PICK)
+    if (!fn) return hipErrorInvalidValue;
+    ZwY2rDev p = *P;
+    void* args[] = {&Y, &U, &V, &ysz, &csz, &w, &h, &ys, &cs, &out, &p};
+    const dim3 grid(((unsigned)w + 2047) / 2048, (unsigned)h / 2 + 1, (unsigned)nframes);  // row pairs (2j-1, 2j)
+    return hipLaunchKernel(fn, grid, dim3(256), args, 0, s);
 }

@@ -36,6 +36,7 @@ __all__ = [
     "rgb_to_yuv420", "loop_filter_frame", "quant_blocks", "transform_quant_blocks", "library_path", "load_library",
     "UpsamplingMethod", "WebPDecoder", "decode_rgb", "decode_rgba", "vp8_decode_rgb", "decode_rgb_batch",
     "decode_rgb_batch_into", "decode_rgba_into", "decode_rgb_into",
+    "decode_batch_device", "decode_batch_device_ptr", "decode_webp_batch_device",
     "yuv_to_rgb", "webp_parse", "encode_frame_lossless", "encode_alpha",
 ]
 
@@ -112,6 +113,13 @@ class _WebpInfo(ctypes.Structure):
                 ("vp8_offset", ctypes.c_uint64), ("vp8_len", ctypes.c_uint64)]
 
 
+class _DeviceImages(ctypes.Structure):
+    _fields_ = [("data", ctypes.c_void_p), ("capacity", ctypes.c_size_t), ("layout", ctypes.c_int),
+                ("dtype", ctypes.c_int), ("channels", ctypes.c_int), ("upsampling", ctypes.c_int),
+                ("frame_stride", ctypes.c_size_t), ("plane_stride", ctypes.c_size_t),
+                ("row_stride", ctypes.c_size_t), ("scale", ctypes.c_float * 4), ("bias", ctypes.c_float * 4)]
+
+
 # (name, restype, argtypes) for every symbol in include/zwebp.h
 _VP, _SZ, _U32, _I, _U8 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint8
 SIGNATURES = [
@@ -139,6 +147,8 @@ SIGNATURES = [
                                      ctypes.POINTER(_Bytes), _VP, _VP]),
     ("zw_vp8_decode_rgb_batch_into", _I, [_VP, _I, ctypes.POINTER(_VP), ctypes.POINTER(_SZ), _I, _I,
                                           ctypes.POINTER(_VP), ctypes.POINTER(_SZ), _U32, _VP, _VP]),
+    ("zw_vp8_decode_batch_device", _I, [_VP, _I, ctypes.POINTER(_VP), ctypes.POINTER(_SZ),
+                                        ctypes.POINTER(_DeviceImages), ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
     ("zw_webp_parse", _I, [_VP, _SZ, ctypes.POINTER(_WebpInfo)]),
     ("zw_webp_decode_into", _I, [_VP, _VP, _SZ, _I, _I, _VP, _SZ, _U32, ctypes.POINTER(_U32),
                                  ctypes.POINTER(_U32)]),
@@ -591,6 +601,149 @@ def decode_rgb_batch_into(frames, outs, bpp=3, upsampling=UpsamplingMethod.Bilin
     return [(ws[i], hs[i]) for i in range(n)]
 
 
+LAYOUTS = {"hwc": 0, "chw": 1}
+DTYPES = {"u8": 0, "f16": 1, "f32": 2}
+
+
+def _layout_code(layout):
+    return LAYOUTS[layout] if isinstance(layout, str) else int(layout)
+
+
+def _dtype_code(dtype):
+    return DTYPES[dtype] if isinstance(dtype, str) else int(dtype)
+
+
+def _vec4(v, default):
+    """scale / bias: None, one number for every channel, or up to 4 per-channel values."""
+    if v is None:
+        return [default] * 4
+    a = [float(x) for x in np.asarray(v, np.float64).reshape(-1)]
+    if len(a) == 1:
+        a = a * 4
+    if len(a) > 4:
+        raise ValueError("at most 4 per-channel values")
+    return a + [default] * (4 - len(a))
+
+
+def decode_batch_device_ptr(frames, ptr, capacity, width=None, height=None, channels=3, layout="chw", dtype="u8",
+                            upsampling=UpsamplingMethod.Bilinear, scale=None, bias=None, frame_stride=None,
+                            plane_stride=None, row_stride=None, ctx=None):
+    """zw_vp8_decode_batch_device, raw-pointer form: n VP8 key frames of one
+    size into device memory at `ptr` (`capacity` elements of `dtype`), HWC
+    (element i*frame_stride + y*row_stride + x*channels + c) or CHW
+    (i*frame_stride + c*plane_stride + y*row_stride + x), strides in elements.
+    Strides left None are the packed ones for `width` x `height` (the frames'
+    size; needed only then).  u8 holds the bytes of decode_rgb_batch (channel 3
+    = 255); f32 holds float32(v) * scale[c] + bias[c] (rounded multiply, rounded
+    add), f16 that value rounded to nearest even.  Returns (width, height) once
+    every write has completed.  The caller makes sure nothing of its own is
+    still queued on that memory."""
+    c = _ctx(ctx)
+    L = c._lib
+    arrs = [_as_u8(d) for d in frames]
+    n = len(arrs)
+    if n == 0:
+        raise ValueError("no frames")
+    lay = _layout_code(layout)
+    if row_stride is None or frame_stride is None or (lay == 1 and plane_stride is None):
+        if width is None or height is None:
+            raise ValueError("width and height size the default strides")
+        if row_stride is None:
+            row_stride = width * channels if lay == 0 else width
+        if plane_stride is None:
+            plane_stride = row_stride * height
+        if frame_stride is None:
+            frame_stride = row_stride * height if lay == 0 else plane_stride * channels
+    out = _DeviceImages(int(ptr), int(capacity), lay, _dtype_code(dtype), int(channels), int(upsampling),
+                        int(frame_stride), int(plane_stride or 0), int(row_stride),
+                        (ctypes.c_float * 4)(*_vec4(scale, 1.0)), (ctypes.c_float * 4)(*_vec4(bias, 0.0)))
+    ptrs = (ctypes.c_void_p * n)(*[a.ctypes.data for a in arrs])
+    lens = (ctypes.c_size_t * n)(*[a.size for a in arrs])
+    w, h = ctypes.c_uint32(), ctypes.c_uint32()
+    _check(L.zw_vp8_decode_batch_device(c.handle, n, ptrs, lens, ctypes.byref(out), ctypes.byref(w), ctypes.byref(h)),
+           "decode_batch_device", DecodingError)
+    return w.value, h.value
+
+
+def decode_batch_device(frames, out=None, channels=3, layout="chw", dtype="u8", upsampling=UpsamplingMethod.Bilinear,
+                        scale=None, bias=None, ctx=None):
+    """n VP8 key frames of one size decoded straight into a torch tensor on the
+    context's device, with no download, upload or host copy
+    (zw_vp8_decode_batch_device; the values are decode_batch_device_ptr's).
+
+    out=None: allocates and returns torch.empty [N, C, H, W] (layout "chw") or
+    [N, H, W, C] ("hwc") of `dtype` ("u8", "f16", "f32") with `channels` 3 or 4.
+    out = a 4-d tensor [N, C, H, W] or [N, H, W, C] (C = 3 or 4 tells which; a
+    tensor both shapes fit is read as `layout`): layout, dtype, channels and
+    strides come from it.  Its innermost stride must be 1 (and the channel
+    stride 1 for HWC): rows, planes and frames may be padded, nothing else;
+    ValueError otherwise, or for a tensor of another device, dtype or size.
+    `capacity` is what the tensor's storage holds from its first element.
+    torch's current stream is synchronised before the call (a recycled
+    allocator block may still have work queued on it); the call returns with
+    every write complete.
+
+    torch must initialise its HIP runtime before libzwebp.so loads in the
+    process: import torch and touch the device (torch.zeros(1, device="cuda"))
+    before the first zwebp call."""
+    import torch
+    c = _ctx(ctx)
+    arrs = [_as_u8(d) for d in frames]
+    n = len(arrs)
+    if n == 0:
+        raise ValueError("no frames")
+    a0 = arrs[0]
+    w = int(a0[6]) | ((int(a0[7]) & 0x3F) << 8) if a0.size >= 10 else 0
+    h = int(a0[8]) | ((int(a0[9]) & 0x3F) << 8) if a0.size >= 10 else 0
+    tdt = {0: torch.uint8, 1: torch.float16, 2: torch.float32}
+    dev = torch.device("cuda", c.device)
+    if out is None:
+        lay, dt = _layout_code(layout), _dtype_code(dtype)
+        if lay not in (0, 1) or dt not in tdt or channels not in (3, 4):
+            raise ValueError("layout hwc | chw, dtype u8 | f16 | f32, channels 3 | 4")
+        # (a frame too short for a header: the smallest tensor; the call reports the decoder's error)
+        shape = (n, channels, max(h, 1), max(w, 1)) if lay == 1 else (n, max(h, 1), max(w, 1), channels)
+        out = torch.empty(shape, dtype=tdt[dt], device=dev)
+    if not isinstance(out, torch.Tensor) or out.dim() != 4:
+        raise ValueError("out must be a 4-d torch tensor")
+    if not out.is_cuda or out.device.index != c.device:
+        raise ValueError(f"out must be on cuda:{c.device}")
+    dts = [k for k, v in tdt.items() if v == out.dtype]
+    if not dts:
+        raise ValueError("out must be uint8, float16 or float32")
+    sh, st = tuple(out.shape), tuple(out.stride())
+    fits_chw = sh[0] == n and sh[1] in (3, 4) and (sh[2], sh[3]) == (h, w)
+    fits_hwc = sh[0] == n and sh[3] in (3, 4) and (sh[1], sh[2]) == (h, w)
+    if fits_chw and fits_hwc:
+        fits_chw = _layout_code(layout) == 1
+    if fits_chw:
+        lay, ch, fs, ps, rs, unit = 1, sh[1], st[0], st[1], st[2], (st[3],)
+    elif fits_hwc:
+        lay, ch, fs, ps, rs, unit = 0, sh[3], st[0], 0, st[1], (1 if st[2] == sh[3] else 0, st[3])
+    else:
+        raise ValueError(f"out must be [{n}, C, {h}, {w}] or [{n}, {h}, {w}, C] with C = 3 or 4")
+    if any(u != 1 for u in unit) or min(fs, ps, rs) < 0:
+        raise ValueError("out: only rows, planes and frames may be padded (innermost stride 1)")
+    capacity = out.untyped_storage().nbytes() // out.element_size() - out.storage_offset()
+    torch.cuda.current_stream(dev).synchronize()
+    decode_batch_device_ptr(arrs, out.data_ptr(), capacity, w, h, ch, lay, dts[0], upsampling, scale, bias, fs, ps, rs,
+                            ctx=c)
+    return out
+
+
+def decode_webp_batch_device(files, out=None, channels=3, layout="chw", dtype="u8",
+                             upsampling=UpsamplingMethod.Bilinear, scale=None, bias=None, ctx=None):
+    """decode_batch_device over lossy WebP files: each RIFF container is
+    stripped with webp_parse (vp8_offset / vp8_len).  ALPH, VP8L and animated
+    files raise DecodingError code 5, as webp_parse does."""
+    vp8 = []
+    for f in files:
+        a = _as_u8(f)
+        info = webp_parse(a)
+        vp8.append(a[info["vp8_offset"]:info["vp8_offset"] + info["vp8_len"]])
+    return decode_batch_device(vp8, out, channels, layout, dtype, upsampling, scale, bias, ctx)
+
+
 def webp_frame_width(vp8):
     """Width field of a VP8 key-frame header (frame tag + start code + 14-bit width);
     0 for a frame too short to hold one (the decode then reports the error)."""
@@ -620,7 +773,7 @@ def decode_rgb_into(data, output, stride_bytes, ctx=None):
 
 
 def decode_rgb_kernel_ms(ctx=None):
-    """Device ms of the last RGB decode batch's k_yuv2rgb launch."""
+    """Device ms of the last RGB decode batch's k_yuv2rgb / k_yuv2rgb_dev launches."""
     c = _ctx(ctx)
     ms = ctypes.c_float()
     _check(c._lib.zw_decode_rgb_kernel_ms(c.handle, ctypes.byref(ms)), "decode_rgb_kernel_ms")

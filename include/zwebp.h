@@ -209,6 +209,50 @@ int zw_vp8_decode_rgb_batch(zw_ctx *ctx, int n, const uint8_t *const *data, cons
 int zw_vp8_decode_rgb_batch_into(zw_ctx *ctx, int n, const uint8_t *const *data, const size_t *lens, int bpp,
                                  int upsampling, uint8_t *const *outs, const size_t *out_lens, uint32_t stride_bytes,
                                  uint32_t *widths, uint32_t *heights);
+/* Device-resident decode (new): n VP8 key frames of one size straight into the
+ * caller's device memory, as a batch tensor.  Nothing crosses to the host: the
+ * conversion kernel (k_yuv2rgb_dev) writes from the decoded planes into `data`.
+ *
+ * Pixel values: frame i, channel c, row y, column x holds exactly the byte
+ * zw_vp8_decode_rgb_batch writes there (fill_rgb / fill_rgba, `upsampling`
+ * ZW_UPSAMPLE_BILINEAR or ZW_UPSAMPLE_SIMPLE); channel 3 is 255.
+ *   ZW_DTYPE_U8  stores that byte v (scale and bias are ignored);
+ *   ZW_DTYPE_F32 stores (float)v * scale[c] + bias[c], a rounded multiply then
+ *                a rounded add (never fused), so a host reproduces it bit for bit;
+ *   ZW_DTYPE_F16 stores that float converted round-to-nearest-even.
+ * Addressing, in elements from `data`:
+ *   ZW_LAYOUT_HWC  i*frame_stride + y*row_stride + x*channels + c,
+ *                  row_stride >= w*channels;
+ *   ZW_LAYOUT_CHW  i*frame_stride + c*plane_stride + y*row_stride + x,
+ *                  row_stride >= w, plane_stride >= (h-1)*row_stride + w.
+ * Frames must not overlap (n > 1: frame_stride >= the elements one frame spans).  The
+ * elements in the gaps (row, plane and frame padding) are never written.
+ *
+ * Checked before anything is queued, each failure ZW_EINVAL: NULL arguments; a
+ * bad layout, dtype, channels (3 | 4) or upsampling; strides below the bounds
+ * above; capacity below the last addressed element + 1; `data` that
+ * hipPointerGetAttributes does not report as device memory on the context's
+ * device (or that is not aligned to its element); a frame of another size
+ * than frame 0, whose header gives the dimensions (a header error returns its
+ * decoder code).
+ *
+ * The call returns after every write has completed (it waits on its own
+ * events), so any stream may read the result afterwards; the caller makes sure
+ * no earlier work of its own still uses `data`.  On error the output's contents
+ * are unspecified and nothing queued outlives the call.  The timing entries
+ * below report this call like any other batch; its download and fan-out stage
+ * times are 0.  *width / *height (may be NULL) receive the frames' size. */
+enum { ZW_LAYOUT_HWC = 0, ZW_LAYOUT_CHW = 1 };
+enum { ZW_DTYPE_U8 = 0, ZW_DTYPE_F16 = 1, ZW_DTYPE_F32 = 2 };
+typedef struct {
+    void *data;          /* device pointer on the context's device */
+    size_t capacity;     /* elements available at data */
+    int layout, dtype, channels /* 3 | 4 */, upsampling;
+    size_t frame_stride, plane_stride /* CHW only */, row_stride; /* in elements */
+    float scale[4], bias[4]; /* float dtypes only */
+} zw_device_images;
+int zw_vp8_decode_batch_device(zw_ctx *ctx, int n, const uint8_t *const *data, const size_t *lens,
+                               const zw_device_images *out, uint32_t *width, uint32_t *height);
 /* WebPDecoder::new (container parse, no decoding; lossy subset: ALPH, VP8L and
  * animation return ZW_EUNSUPPORTED with info filled as far as parsed). */
 int zw_webp_parse(const uint8_t *data, size_t len, zw_webp_info *info);
