@@ -12,7 +12,7 @@
 #include <vector>
 
 #include "../../include/zwebp.h"
-#include "zw_host_entropy.h"
+#include "zw_vp8_tables.h"
 #include "zw_tokl.h"
 
 using namespace zwh;

@@ -30,7 +30,7 @@
 
 #include "../../include/zwebp.h"
 #include "zw_common.h"
-#include "zw_host_entropy.h"
+#include "zw_host_emit.h"
 #include "zw_host_internal.h"
 #include "zw_progress.h"
 
@@ -439,7 +439,7 @@ static int device_cus(int device)
 }
 
 // encode_frame_lossy's dimension rule (vp8.rs:3143-3148): any u16, the header
-// keeping the low 14 bits (vp8.rs:326-327; zwh::emit_frame does the same).
+// keeping the low 14 bits (vp8.rs:326-327; zwh::assemble_frame does the same).
 // Zero is refused (the reference has no meaningful zero-MB frame).  Frames
 // wider than the batch kernels' LDS takes (zwk_encode_max_mbw(0), 1 560 MBs)
 // run the row-parallel kernels, whose LDS holds any u16 width.
@@ -1042,25 +1042,6 @@ static int chunk_pass2(zw_pipe* p, PipeLane& L, int fa, int na, bool timed)
     return ZW_OK;
 }
 
-// One frame's VP8 bitstream from its pass-2 records.  With token partitions
-// and a chunk of one frame (a single-frame call) the partitions are coded on
-// their own threads; otherwise the frame's thread codes them in turn.
-static void emit_vp8(zw_pipe* p, std::vector<uint8_t>& out, const uint8_t* rec, size_t hf, int na)
-{
-    const uint8_t(*upd)[8][3][11] = (const uint8_t(*)[8][3][11])(p->h_upd.data() + hf * 4 * 8 * 3 * 11);
-    const ZwFrameParams& P = p->h_params[hf];
-    if (p->nparts == 1) {
-        zwh::emit_frame(out, P, rec, p->w, p->h, p->h_have_upd[hf] != 0, upd);
-    } else if (na == 1) {
-        zwh::emit_frame_parts(out, P, rec, p->w, p->h, p->h_have_upd[hf] != 0, upd, p->nparts,
-                              [](int n, auto fn) { parallel_for(n, fn); });
-    } else {
-        zwh::emit_frame_parts(out, P, rec, p->w, p->h, p->h_have_upd[hf] != 0, upd, p->nparts, [](int n, auto fn) {
-            for (int i = 0; i < n; i++) fn(i);
-        });
-    }
-}
-
 // ZW_DUMP_EMIT=<path>: the emission input of the pipe's frame 0 (its
 // parameters, probability updates and packed records) for tools/emit_bench.cpp.
 static void dump_emit_input(zw_pipe* p, const uint8_t* rec, size_t bytes, size_t hf)
@@ -1111,9 +1092,9 @@ struct EmitWsLease {
     }
 };
 
-// One emission task: frames [i0, i0 + K) of the chunk [fa, fa + na), coded in
-// the calling thread with workspace ws.
-static int emit_task(zw_pipe* p, const FetchBuf& B, int fa, int na, int par, int i0, int K, zwh::EmitWs* ws)
+// One emission task: frames [i0, i0 + K) of the chunk that starts at frame fa,
+// all their token partitions coded in the calling thread with workspace ws.
+static int emit_task(zw_pipe* p, const FetchBuf& B, int fa, int par, int i0, int K, zwh::EmitWs* ws)
 {
     const size_t F = (size_t)fa;
     const bool has_alpha = p->color == ZW_COLOR_LA8 || p->color == ZW_COLOR_RGBA8;
@@ -1127,25 +1108,21 @@ static int emit_task(zw_pipe* p, const FetchBuf& B, int fa, int na, int par, int
         outs[k] = p->container ? &vp8[k] : &p->bitstreams[f];
         outs[k]->clear();
     }
-    if (p->nparts == 1) {
-        const ZwFrameParams* Pk[zwh::EmitWs::kMax];
-        const uint8_t* rk[zwh::EmitWs::kMax];
-        bool hk[zwh::EmitWs::kMax];
-        const uint8_t(*uk[zwh::EmitWs::kMax])[8][3][11];
-        for (int k = 0; k < K; k++) {
-            const size_t hf = hidx(p, par, F + i0 + k);
-            Pk[k] = &p->h_params[hf];
-            rk[k] = B.pack + B.finfo[2 * (i0 + k)];
-            hk[k] = p->h_have_upd[hf] != 0;
-            uk[k] = (const uint8_t(*)[8][3][11])(p->h_upd.data() + hf * 4 * 8 * 3 * 11);
-        }
-        try {
-            zwh::emit_frames(outs, Pk, rk, K, p->w, p->h, hk, uk, ws);
-        } catch (const std::bad_alloc&) {  // (the worst-case decision arenas)
-            return ZW_ENOMEM;
-        }
-    } else {
-        emit_vp8(p, *outs[0], B.pack + B.finfo[2 * i0], hidx(p, par, F + i0), na);
+    const ZwFrameParams* Pk[zwh::EmitWs::kMax];
+    const uint8_t* rk[zwh::EmitWs::kMax];
+    bool hk[zwh::EmitWs::kMax];
+    const uint8_t(*uk[zwh::EmitWs::kMax])[8][3][11];
+    for (int k = 0; k < K; k++) {
+        const size_t hf = hidx(p, par, F + i0 + k);
+        Pk[k] = &p->h_params[hf];
+        rk[k] = B.pack + B.finfo[2 * (i0 + k)];
+        hk[k] = p->h_have_upd[hf] != 0;
+        uk[k] = (const uint8_t(*)[8][3][11])(p->h_upd.data() + hf * 4 * 8 * 3 * 11);
+    }
+    try {
+        zwh::emit_frames(outs, Pk, rk, K, p->nparts, p->w, p->h, hk, uk, ws);
+    } catch (const std::bad_alloc&) {  // (the worst-case decision arenas)
+        return ZW_ENOMEM;
     }
     if (!p->container) return ZW_OK;
     for (int k = 0; k < K; k++) {
@@ -1168,10 +1145,12 @@ static int chunk_emit(zw_pipe* p, const FetchBuf& B, int fa, int na, int par, st
 {
     if (fa == 0) dump_emit_input(p, B.pack + B.finfo[0], (size_t)B.finfo[1], hidx(p, par, 0));
     std::atomic<int> err{ZW_OK};
-    // One token partition (the default): the frames go out in groups of up to
-    // ZW_EMIT_GROUP (16 on a host with AVX-512: their boolean coders run as the
-    // lanes of one vector coder, zwh::raw_code16; else 4, interleaved), in one
-    // thread each (zwh::emit_frames); with token partitions, one frame per task.
+    // The frames go out in groups, one thread each (zwh::emit_frames), of up to
+    // ZW_EMIT_GROUP streams -- a stream is one (frame, token partition) pair, so
+    // with one partition (the default) it counts frames, else a group holds
+    // ZW_EMIT_GROUP / partitions frames, at least one.  16 on a host with
+    // AVX-512 (the streams' boolean coders run as the lanes of one vector
+    // coder, zwh::raw_code16), else 4, interleaved.
     static const int group = [] {
         const char* e = getenv("ZW_EMIT_GROUP");
         const int g = e && *e ? atoi(e) : (zwh::have_code16() ? 16 : 4);
@@ -1180,10 +1159,9 @@ static int chunk_emit(zw_pipe* p, const FetchBuf& B, int fa, int na, int par, st
     // (small chunks -- the seam's batches -- in smaller groups, so that every worker has one)
     // (and very large frames in groups whose decision arenas stay within 1 GiB of
     // address space a worker)
-    const int gmem = (int)std::max<size_t>(1, ((size_t)1 << 30) / zwh::emit_arena_bytes(p->mbw, p->mbh));
-    const int G = p->nparts != 1
-                      ? 1
-                      : std::max(1, std::min({group, gmem, std::max(4, na / std::max(1, host_threads()))}));
+    const int gmem = (int)std::max<size_t>(1, ((size_t)1 << 30) / zwh::emit_arena_bytes(p->mbw, p->mbh, p->nparts));
+    const int streams = std::min(group, std::max(4, na / std::max(1, host_threads())));
+    const int G = std::max(1, std::min(streams / p->nparts, gmem));
     // workers per lane (ZW_EMIT_THREADS; default every host thread: with 8 a lane, the
     // two lanes' emissions used 2 % less CPU but the step was 2 % slower)
     static const int per_lane_env = [] { const char* e = getenv("ZW_EMIT_THREADS"); return e ? atoi(e) : 0; }();
@@ -1191,7 +1169,7 @@ static int chunk_emit(zw_pipe* p, const FetchBuf& B, int fa, int na, int par, st
     parallel_for((na + G - 1) / G, [&](int g) {
         EmitWsLease lease(p, cpu_ns);
         const int i0 = g * G;
-        const int r = lease.ws ? emit_task(p, B, fa, na, par, i0, std::min(G, na - i0), lease.ws.get()) : ZW_ENOMEM;
+        const int r = lease.ws ? emit_task(p, B, fa, par, i0, std::min(G, na - i0), lease.ws.get()) : ZW_ENOMEM;
         int ok = ZW_OK;
         if (r) err.compare_exchange_strong(ok, r);
     }, nt);

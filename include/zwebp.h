@@ -156,7 +156,7 @@ int zw_encode_frame_lossy(zw_ctx *ctx, const uint8_t *data, size_t len, uint32_t
  * pinned by any reference fixture; the checks are the oracle's identical
  * bytes plus libwebp / device decodes to the same pixels.  1 gives
  * encode_frame_lossy's bytes.  A single frame's partitions are entropy-coded
- * on parallel host threads.  ZW_EINVAL for any other count. */
+ * side by side on one host thread.  ZW_EINVAL for any other count. */
 int zw_encode_frame_lossy_ex(zw_ctx *ctx, const uint8_t *data, size_t len, uint32_t width, uint32_t height,
                              int color, uint8_t quality, uint8_t method, int token_partitions, zw_bytes *out);
 

@@ -10,9 +10,10 @@ CPU tests pin the oracle's partitioned streams: the reference-layout decoder
 restatement and the system libwebp (an independent decoder) decode every
 partition count to the same pixels as the one-partition stream, and the layout
 fields are where the format puts them.  GPU tests: the product's partitioned
-bitstreams are byte-equal to the oracle's, on the single-frame path (partitions
-coded on parallel host threads) and the batch path, and the device decoder
-reads them back.
+bitstreams are byte-equal to the oracle's, on the single-frame path (one
+emission task, the partitions' coders side by side in it) and the batch path
+(groups of frames x partitions, up to 16 streams a task), and the device
+decoder reads them back.
 """
 import ctypes
 import struct
@@ -147,6 +148,22 @@ def test_gpu_partitions_batch(ctx):
     # the single-frame path with one partition still gives the reference bytes
     one = zwebp.encode_frame_lossy(imgs[0], w, h, zwebp.ColorType.Rgba8, 75, 4, ctx=ctx)
     assert one == O.encode(imgs[0], w, h, 3, 75, 4)[1]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [2, 8])
+def test_gpu_partitions_batch_groups(ctx, n):
+    """Nine frames of 3 x 7 MBs: emission groups of more than one frame (a
+    small batch goes out in groups of 4 streams: two frames with 2 partitions,
+    one with 8), a last group of one, and a row count that n does not divide."""
+    import zwebp
+    w, h = 48, 104
+    imgs = [synth_rgba(w, h, 0x5EED0200 + i) for i in range(9)]
+    outs = zwebp.encode_batch(imgs, w, h, zwebp.ColorType.Rgba8, 75, 4, ctx=ctx, token_partitions=n)
+    assert len(outs) == 9
+    for i, img in enumerate(imgs):
+        rc, ref, _ = O.encode(img, w, h, 3, 75, 4, nparts=n)
+        assert rc == 0 and outs[i] == ref, (n, i)
 
 
 @pytest.mark.gpu

@@ -3,7 +3,7 @@
 #include <chrono>
 #include <cstdio>
 #include <random>
-#include "zw_host_entropy.h"
+#include "emit_ref.h"
 int main(int argc, char** argv)
 {
     const int n = argc > 1 ? atoi(argv[1]) : 2000000;

@@ -10,7 +10,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
-#include "zw_host_entropy.h"
+#include "zw_host_emit.h"
+#include "emit_ref.h"
 
 static uint64_t fnv(const std::vector<uint8_t>& v)
 {
@@ -168,10 +169,22 @@ int main(int argc, char** argv)
         const uint8_t* recs[4] = {rec.data(), rec.data(), rec.data(), rec.data()};
         const bool haves[4] = {have != 0, have != 0, have != 0, have != 0};
         const uint8_t(*upds[4])[8][3][11] = {upd, upd, upd, upd};
-        const double t = best_ms(reps, [&] { zwh::emit_frames(op, Ps, recs, K, w, h, haves, upds); });
+        const double t = best_ms(reps, [&] { zwh::emit_frames(op, Ps, recs, K, 1, w, h, haves, upds); });
         bool same = true;
         for (int k = 0; k < K; k++) same = same && o[k] == ref;
         printf("  emit_frames K=%d: %.3f ms per frame, %s\n", K, t / K, same ? "identical" : "DIFFERENT");
+    }
+    // the frame with 8 token partitions: its 8 streams side by side (a single-frame call's shape)
+    {
+        std::vector<uint8_t> r8, o8;
+        std::vector<uint8_t>* op = &o8;
+        const ZwFrameParams* Ps = &P;
+        const uint8_t* recs = rec.data();
+        const bool haves = have != 0;
+        const uint8_t(*upds)[8][3][11] = upd;
+        const double tr = best_ms(reps, [&] { zwh::emit_frame(r8, P, rec.data(), w, h, have != 0, upd, 8); });
+        const double t8 = best_ms(reps, [&] { zwh::emit_frames(&op, &Ps, &recs, 1, 8, w, h, &haves, &upds); });
+        printf("  8 partitions: serial walk %.3f ms, emit_frames %.3f ms, %s\n", tr, t8, o8 == r8 ? "identical" : "DIFFERENT");
     }
     // distinct: K = 4 different frames, as the pipeline's groups have (the same
     // frame four times lets the branch predictor learn each row's branches):
@@ -208,7 +221,7 @@ int main(int argc, char** argv)
             for (int r = 0; r < nr; r++) {
                 for (size_t i = 0; i < sweep.size(); i += 64) sweep[i]++;
                 const auto t0 = std::chrono::steady_clock::now();
-                for (int k0 = 0; k0 < 16; k0 += K) zwh::emit_frames(op + k0, Ps + k0, recs + k0, K, w, h, haves + k0, upds + k0);
+                for (int k0 = 0; k0 < 16; k0 += K) zwh::emit_frames(op + k0, Ps + k0, recs + k0, K, 1, w, h, haves + k0, upds + k0);
                 const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
                 best = ms < best ? ms : best;
                 sum += ms;
@@ -270,12 +283,7 @@ int main(int argc, char** argv)
     });
     printf("  walk parts: record views %.3f ms, + MB headers %.3f ms\n", t_view, t_hdr);
     (void)sink;
-    auto reset = [](zwh::RawBool& S) {
-        S.lo = S.pos = 1;
-        S.low = 0;
-        S.range = 255;
-        S.count = -24;
-    };
+    auto reset = [](zwh::RawBool& S) { S.reset(); };
     zwh::RawBool Q[4];
     zwh::RawBool* qp[4] = {&Q[0], &Q[1], &Q[2], &Q[3]};
     const uint16_t* dp[4] = {all.data(), all.data(), all.data(), all.data()};

@@ -1,14 +1,43 @@
 // Equivalence of the split emission (zwh::emit_frames: recorded decisions,
-// K frames' coders interleaved) with zwh::emit_frame, and of the interleaved
-// coder (raw_code_multi) with the reference's bit-at-a-time encoder, on
-// synthetic inputs: random packed MB records (every luma mode, skips, segments,
-// sub-modes, levels of every token category and sign, empty and full blocks)
-// and random decision streams with long carry runs.
+// K frames x n token partitions' coders side by side) with the serial walk
+// (zwh::emit_frame, emit_ref.h), and of the interleaved and 16-lane coders with
+// the reference's bit-at-a-time encoder, on synthetic inputs: random packed MB
+// records (every luma mode, skips, segments, sub-modes, levels of every token
+// category and sign, empty and full blocks) and random decision streams with
+// long carry runs.  Last, a workspace whose token arena fails to grow is used
+// again (left out of an AddressSanitizer build, which has its own allocator).
 //   g++ -O2 -std=c++17 -I image-webp_amd/csrc tools/emit_equiv.cpp
 #include <cstdio>
 #include <algorithm>
+#include <new>
 #include <random>
-#include "zw_host_entropy.h"
+#include "zw_host_emit.h"
+#include "emit_ref.h"
+
+#if defined(__SANITIZE_ADDRESS__)
+#define EQUIV_FAIL_NEW 0
+#elif defined(__has_feature)
+#if __has_feature(address_sanitizer)
+#define EQUIV_FAIL_NEW 0
+#endif
+#endif
+#ifndef EQUIV_FAIL_NEW
+#define EQUIV_FAIL_NEW 1
+#endif
+
+#if EQUIV_FAIL_NEW
+// operator new[] (the decision arenas' allocator) failing once on request:
+// the fail_new_in-th call from now throws
+static int fail_new_in = 0;
+void* operator new[](size_t n)
+{
+    if (fail_new_in > 0 && --fail_new_in == 0) throw std::bad_alloc();
+    if (void* p = malloc(n ? n : 1)) return p;
+    throw std::bad_alloc();
+}
+void operator delete[](void* p) noexcept { free(p); }
+void operator delete[](void* p, size_t) noexcept { free(p); }
+#endif
 
 static std::mt19937 rng(11);
 static int rnd(int n) { return (int)(rng() % (uint32_t)n); }
@@ -43,6 +72,57 @@ static std::vector<uint8_t> synth_records(int mbw, int mbh, int style)
     }
     return r;
 }
+
+// K random frames of mbw x mbh MBs: parameters, probability updates, records
+struct FrameSet {
+    int K;
+    std::vector<ZwFrameParams> P;
+    std::vector<std::vector<uint8_t>> rec;
+    std::vector<uint8_t> upd;  // [K][4][8][3][11]
+    bool have[16];
+    FrameSet(int K_, int mbw, int mbh, int style) : K(K_), P(K_), rec(K_), upd((size_t)K_ * 4 * 8 * 3 * 11)
+    {
+        for (int k = 0; k < K; k++) {
+            ZwFrameParams& p = P[k];
+            memset(&p, 0, sizeof p);
+            p.width = mbw * 16 - rnd(15);
+            p.height = mbh * 16 - rnd(15);
+            p.mbw = mbw;
+            p.mbh = mbh;
+            p.seg_enabled = rnd(2);
+            p.seg_update_map = p.seg_enabled && rnd(2);
+            for (int i = 0; i < 3; i++) p.seg_probs[i] = (uint8_t)(rnd(3) ? 1 + rnd(254) : 255);
+            for (int s = 0; s < 4; s++) p.seg[s].quantizer_level = rnd(2) ? rnd(60) - 30 : 0;
+            p.base_qi = rnd(128);
+            p.filter_level = rnd(64);
+            p.skip_prob = 1 + rnd(254);
+            have[k] = rnd(2);
+            for (int i = 0; i < 4 * 8 * 3 * 11; i++) upd[(size_t)k * 4 * 8 * 3 * 11 + i] = (uint8_t)(1 + rnd(255));
+            rec[k] = synth_records(mbw, mbh, style);
+        }
+    }
+    const uint8_t (*upd_of(int k) const)[8][3][11] { return (const uint8_t(*)[8][3][11])(upd.data() + (size_t)k * 4 * 8 * 3 * 11); }
+    // emit_frames with n token partitions (workspace ws, or the thread's own)
+    // against the serial walk: the first frame that differs, or -1
+    int differs(int n, zwh::EmitWs* ws = nullptr) const
+    {
+        std::vector<uint8_t> got[16], ref;
+        std::vector<uint8_t>* gp[16];
+        const ZwFrameParams* pp[16];
+        const uint8_t* rp[16];
+        const uint8_t(*up[16])[8][3][11];
+        for (int k = 0; k < K; k++) gp[k] = &got[k], pp[k] = &P[k], rp[k] = rec[k].data(), up[k] = upd_of(k);
+        zwh::emit_frames(gp, pp, rp, K, n, P[0].width, P[0].height, have, up, ws);
+        for (int k = 0; k < K; k++) {
+            zwh::emit_frame(ref, P[k], rec[k].data(), P[0].width, P[0].height, have[k], upd_of(k), n);
+            if (ref != got[k]) {
+                printf("emit MISMATCH frame %d of %d, %d partitions (%zu vs %zu bytes)\n", k, K, n, got[k].size(), ref.size());
+                return k;
+            }
+        }
+        return -1;
+    }
+};
 
 int main()
 {
@@ -146,48 +226,48 @@ int main()
     } else {
         printf("(no AVX-512 here: the 16-lane coder not checked)\n");
     }
-    // 2) emit_frames (K = 1..16 frames of mixed content) against emit_frame
-    for (int trial = 0; trial < 40; trial++) {
-        const int K = 1 + trial % 16;
-        const int mbw = 1 + rnd(9), mbh = 1 + rnd(7);
-        std::vector<ZwFrameParams> P(K);
-        std::vector<std::vector<uint8_t>> rec(K);
-        static uint8_t upd[16][4][8][3][11];
-        bool have[16];
-        for (int k = 0; k < K; k++) {
-            ZwFrameParams& p = P[k];
-            memset(&p, 0, sizeof p);
-            p.width = mbw * 16 - rnd(15);
-            p.height = mbh * 16 - rnd(15);
-            p.mbw = mbw;
-            p.mbh = mbh;
-            p.seg_enabled = rnd(2);
-            p.seg_update_map = p.seg_enabled && rnd(2);
-            for (int i = 0; i < 3; i++) p.seg_probs[i] = (uint8_t)(rnd(3) ? 1 + rnd(254) : 255);
-            for (int s = 0; s < 4; s++) p.seg[s].quantizer_level = rnd(2) ? rnd(60) - 30 : 0;
-            p.base_qi = rnd(128);
-            p.filter_level = rnd(64);
-            p.skip_prob = 1 + rnd(254);
-            have[k] = rnd(2);
-            for (size_t i = 0; i < sizeof upd[k]; i++) (&upd[k][0][0][0][0])[i] = (uint8_t)(1 + rnd(255));
-            rec[k] = synth_records(mbw, mbh, trial % 3);
-        }
-        std::vector<uint8_t> got[16], ref;
-        std::vector<uint8_t>* gp[16];
-        for (int k = 0; k < 16; k++) gp[k] = &got[k];
-        const ZwFrameParams* pp[16];
-        const uint8_t* rp[16];
-        const uint8_t(*up[16])[8][3][11];
-        for (int k = 0; k < K; k++) pp[k] = &P[k], rp[k] = rec[k].data(), up[k] = upd[k];
-        zwh::emit_frames(gp, pp, rp, K, P[0].width, P[0].height, have, up);
-        for (int k = 0; k < K; k++) {
-            zwh::emit_frame(ref, P[k], rec[k].data(), P[0].width, P[0].height, have[k], upd[k]);
-            if (ref != got[k]) {
-                printf("emit MISMATCH trial %d frame %d (%zu vs %zu bytes)\n", trial, k, got[k].size(), ref.size());
+    // 2) emit_frames (n = 1, 2, 4, 8 token partitions, K = 1..16 / n frames of
+    // mixed content, 1..19 MB rows: fewer rows than partitions and row counts
+    // that n does not divide among them) against the serial walk
+    for (int n = 1; n <= 8; n *= 2) {
+        int few = 0, ragged = 0;
+        for (int trial = 0; trial < (n == 1 ? 48 : 32); trial++) {
+            const int K = 1 + trial % (16 / n);
+            const int mbw = 1 + rnd(9), mbh = n > 1 && trial % 4 == 1 ? 1 + rnd(n - 1) : 1 + rnd(19);
+            few += mbh < n;
+            ragged += mbh > n && mbh % n != 0;
+            if (FrameSet(K, mbw, mbh, trial % 3).differs(n) >= 0) {
+                printf("(trial %d, %d x %d MBs)\n", trial, mbw, mbh);
                 return 1;
             }
         }
+        if (n > 1 && (few == 0 || ragged == 0)) {
+            printf("%d partitions: no trial with fewer rows (%d) or a ragged last band (%d)\n", n, few, ragged);
+            return 1;
+        }
     }
+#if EQUIV_FAIL_NEW
+    // 3) a workspace whose token arena fails to grow: std::bad_alloc, and the
+    // workspace emits again -- first frames that fit what it held before
+    {
+        std::unique_ptr<zwh::EmitWs> ws(new zwh::EmitWs);
+        const FrameSet small(2, 2, 3, 0), large(4, 5, 7, 2);
+        if (small.differs(2, ws.get()) >= 0) return 1;
+        bool threw = false;
+        fail_new_in = 2;  // the header arena's growth, then the token arena's
+        try {
+            (void)large.differs(4, ws.get());
+        } catch (const std::bad_alloc&) {
+            threw = true;
+        }
+        if (!threw || fail_new_in != 0) {
+            printf("failed growth: no std::bad_alloc from the token arena\n");
+            return 1;
+        }
+        if (small.differs(2, ws.get()) >= 0 || large.differs(4, ws.get()) >= 0) return 1;
+        printf("failed growth survived\n");
+    }
+#endif
     printf("equivalent\n");
     return 0;
 }
