@@ -16,12 +16,15 @@
 // and runs on wave 0 while waves 1..NW-1 do the luma wavefront.
 #include "zw_dev.h"
 
+#include <type_traits>
+
 #include "zw_enc_rows.h"
 
 // ---------------------------------------------------------------------------
 // Compile-time knobs (make exp EXPDEFS="-DZW_...=..."), each with the
 // measurement that set its default.  The row schedule's (ZW_P1_ORDER,
-// ZW_P1_SLOWSKIP, ZW_P1_SLOW_NUM / _DEN) are in zw_enc_rows.h.
+// ZW_P1_SLOWSKIP, ZW_P1_SLOW_NUM / _DEN; in frame pairs ZW_P1P_SLOW_NUM / _DEN,
+// ZW_P1P_JOIN_NUM / _DEN / _MIN) are in zw_enc_rows.h.
 // ---------------------------------------------------------------------------
 // Waves per workgroup of each encode pass.  Both kernels stay within 168
 // VGPRs, so three waves share each SIMD (12 per CU); ZW_NW sets both.
@@ -47,11 +50,14 @@
 #endif
 #ifndef ZW_P1_LUMA_MAX
 #define ZW_P1_LUMA_MAX 3  // (2 kept the luma waves below the chroma chain: 0.7 % slower)
-#endif
+#endif                    // (frame pairs with the chain waves joining, 512 1080p frames: 3 46.13-46.26, 2 46.23-46.30 ms)
 // The chroma chain is pass 1's critical path: it takes issue priority over the
 // luma waves sharing its SIMD (measured: 47.6 -> 44.3 ms per 256 1080p frames
 // against luma-first priority at 12 waves).  Pass 1's luma waves start below
 // it: the chain sets the pass's length once 11 waves share the luma wavefront.
+// (Frame pairs, where the chain waves take luma rows after their chains, 512
+// 1080p frames, join at 5/8 and slow share 2/1: priority 3 46.13-46.26, 2
+// 46.14-46.25 ms: no difference.)
 #ifndef ZW_CHAIN_PRIO
 #define ZW_CHAIN_PRIO 3
 #endif
@@ -3093,11 +3099,10 @@ __device__ __forceinline__ void encode_body(const EncArgs& a)
         __builtin_amdgcn_s_setprio(ZW_CHAIN_PRIO);
         // frame pairs: chain wave k works frame f + k
         const int cfr = PAIR ? wv : 0;
-        if (PAIR && cfr >= nf) {
-            ph_flush();
-            return;
-        }
-        const int fc = f + cfr;
+        // (the odd last workgroup of a pair launch: chain wave 1 has no frame,
+        // only its luma rows; it points at frame f and runs no chain row)
+        const bool has_chain = !PAIR || cfr < nf;
+        const int fc = f + (has_chain ? cfr : 0);
         const uint8_t* const lutc = seg_lut + L.sL * cfr;
         int8_t* const tdc = top_derr + L.sd * cfr;
         if (PAIR) {
@@ -3171,7 +3176,7 @@ __device__ __forceinline__ void encode_body(const EncArgs& a)
             return;
         }
         MbFetch nx = fetch_mb(&a, fc, lane, 0, 0);
-        for (int mby = 0; mby < mbh; mby++) {
+        for (int mby = 0; has_chain && mby < mbh; mby++) {
             if (lane < 12) {
                 C.M->left_u[lane] = 129;
                 C.M->left_v[lane] = 129;
@@ -3200,9 +3205,21 @@ __device__ __forceinline__ void encode_body(const EncArgs& a)
                 wsync();
             }
         }
-        for (int i = lane; i < mbw * 4; i += 64) a.derr[(size_t)fc * mbw * 4 + i] = tdc[i];
-        ph_flush();
-        return;
+        for (int i = lane; has_chain && i < mbw * 4; i += 64) a.derr[(size_t)fc * mbw * 4 + i] = tdc[i];
+        if (!PAIR) {
+            ph_flush();
+            return;
+        }
+        // frame pairs: its chain done, the wave takes luma rows (PairRowSchedule1,
+        // from the join row on); C back to the workgroup's first frame
+        C.f = f;
+        C.P = P;
+        C.T = T;
+        C.Sl = Sl;
+        C.top_u = top_u;
+        C.top_v = top_v;
+        C.top_derr = top_derr;
+        C.method = __builtin_amdgcn_readfirstlane(P->method);
     }
 
     if (PASS == 1) __builtin_amdgcn_s_setprio(ZW_LUMA_PRIO);
@@ -3294,8 +3311,9 @@ __device__ __forceinline__ void encode_body(const EncArgs& a)
     };
     if constexpr (PAIR) {
         // ---- frame pairs: every wave works MB row y of both frames of the
-        // workgroup (the rows of a frame go to the waves as in the one-frame
-        // kernel), MB (x, y) of frame 0 and of frame 1 per iteration.  Both
+        // workgroup (which wave takes which row: RP below; in pass 1 the chain
+        // waves arrive here after their chains and take rows from the join row
+        // on), MB (x, y) of frame 0 and of frame 1 per iteration.  Both
         // frames' rows advance together, so one progress word per wave serves
         // both.  The two MBs' I4 searches run in one wave (pick_i4_pair): lanes
         // 0..31 frame 0, lanes 32..63 frame 1.  The other per-MB stages run in
@@ -3308,16 +3326,17 @@ __device__ __forceinline__ void encode_body(const EncArgs& a)
         const int meth1 = nf == 2 ? __builtin_amdgcn_readfirstlane(a.params[f + 1].method) : C.method;
         const bool trel1 = PASS == 2 && nf == 2 && __builtin_amdgcn_readfirstlane(a.params[f + 1].do_trellis);
         const bool keep1 = !trel1 && (PASS == 1 || a.dbg == nullptr);
-        // the luma waves (pass 1: after the chain waves) take the rows in turn
-        using RP = RowSchedule<PASS, ROWS, NW, NCW, true>;
+        // pass 2: the waves take the rows in turn; pass 1: fewer rows for the
+        // luma waves beside a chain, and from the join row on the chain waves'
+        // too (PairRowSchedule1)
+        using RP =
+            typename std::conditional<PASS == 1, PairRowSchedule1<NW, NCW>, RowSchedule<PASS, ROWS, NW, NCW, true>>::type;
         const bool same_k = nf == 1 || (meth1 == C.method && trel1 == trel);
-        for (int it = 0;; it++) {
-            const int mby = RP::first_row(wv, mbh) + it * RP::nrw;
-            if (mby >= mbh) break;
+        for (int mby = RP::first_row(wv, mbh); mby < mbh; mby = RP::next_row(wv, mby, mbh)) {
 #pragma unroll
             for (int fr = 0; fr < 2; fr++) row_start(Mp[fr], lane);
             wsync();
-            const int prevw = mby > 0 ? RP::wave_of_row(mby - 1) : 0;
+            const int prevw = mby > 0 ? RP::wave_of_row(mby - 1, mbh) : 0;
             auto wait_above = [&](int need) {
                 if (mby > 0) wait_row(progress, prevw, (mby - 1) * 65536 + need);
             };
