@@ -19,6 +19,10 @@
 #include <type_traits>
 
 #include "zw_enc_rows.h"
+#include "zw_enc_pairfinal.h"
+
+// Phase counters of the profiling build (tools/phase_prof.py names them).
+#define ZW_PH_N 28
 
 // ---------------------------------------------------------------------------
 // Compile-time knobs (make exp EXPDEFS="-DZW_...=..."), each with the
@@ -683,14 +687,15 @@ struct WaveLds {
     int V[2][40];                 // I4 value vectors of the (up to) two sub-blocks of a search step
     int nzt[4], nzl[4];
     int misc[16];
-    uint32_t pst[2][4];           // paired kernels: per MB {lm | need << 4 | seg << 8, i16 score lo, hi, i4 nz | win << 16}
+    uint32_t pst[2][4];           // paired kernels: per MB {lm | need << 4 | seg << 8, i16 score lo, hi, i4 nz | win << 16};
+                                  // after the searches [1] = final chroma's result | cm << 9, [2] = final luma's result
     // row-parallel kernels: this MB's slice of the row above's state (top_y of
     // the MB and of the MB above-right, top_u/v, top_c, top_derr), pulled from
     // and pushed to global memory around each MB
     uint8_t win_y[32], win_u[8], win_v[8], win_c[12];
     int8_t win_d[4];
 #ifdef ZW_PHASE_PROF
-    unsigned long long ph[24];
+    unsigned long long ph[ZW_PH_N];
 #endif
 };
 
@@ -876,8 +881,8 @@ __device__ void pick_i16(const Ctx& C, int& best_mode, unsigned long long& best_
 
 #ifdef ZW_PHASE_PROF
 // Per-phase cycle counters (profiling builds only): [pass-1][phase].
-__device__ unsigned long long zw_phase_cycles_dev[2][24];
-__device__ unsigned long long zw_wave_cycles_dev[2][16][24];  // the same per wave index
+__device__ unsigned long long zw_phase_cycles_dev[2][ZW_PH_N];
+__device__ unsigned long long zw_wave_cycles_dev[2][16][ZW_PH_N];  // the same per wave index
 #define PH_START() long long ph_t_ = clock64()
 #define PH_RESET() (ph_t_ = clock64())
 #define PH_MARK(k) PH_MARK_L(k, lane, PASS)
@@ -892,7 +897,7 @@ extern "C" int zw_wave_cycles(unsigned long long* out, int reset)
 {
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(zw_wave_cycles_dev), sizeof(zw_wave_cycles_dev)) != hipSuccess) return -1;
     if (reset) {
-        static unsigned long long z[2][16][24];
+        static unsigned long long z[2][16][ZW_PH_N];
         if (hipMemcpyToSymbol(HIP_SYMBOL(zw_wave_cycles_dev), z, sizeof z) != hipSuccess) return -1;
     }
     return 0;
@@ -901,7 +906,7 @@ extern "C" int zw_phase_cycles(unsigned long long* out, int reset)
 {
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(zw_phase_cycles_dev), sizeof(zw_phase_cycles_dev)) != hipSuccess) return -1;
     if (reset) {
-        static unsigned long long z[2][24];
+        static unsigned long long z[2][ZW_PH_N];
         if (hipMemcpyToSymbol(HIP_SYMBOL(zw_phase_cycles_dev), z, sizeof z) != hipSuccess) return -1;
     }
     return 0;
@@ -2321,6 +2326,236 @@ __device__ int final_luma(const Ctx& C, int mode, bool trel, int y_nz_out[16], i
     return anynz;
 }
 
+// The final I16 luma transform (final_luma, mode != 4) of both MBs of a frame
+// pair in one pass of the wave: frame 0's MB in lanes 0..31, frame 1's in
+// lanes 32..63, lane 16 k + b of a half holding block b (a half's second group
+// repeats the first; the first stores).  Each frame uses its own segment,
+// tables, borders and MbLds.  With the trellis, a block runs only under the
+// start contexts its neighbours leave open and not at all when the trellis
+// can only return zeros (zw_enc_pairfinal.h): the two MBs' runs are numbered
+// onto the wave's lanes and, when they are 64 at the most, worked in one
+// trellis call (their coefficients go to the task lanes through C.M->lev[b],
+// not yet written; the task table through W->dc); otherwise in one call per
+// frame with every block under every context, as final_luma does.  The context
+// chains are then resolved on the scalar unit, per frame, and every block
+// gathers its resolved context's levels from the lane that ran it.
+// res: the MB's per-block has-coefficients flags (bits 0..15) and the
+// simple-quant "any nonzero" flag (bit 16), as final_luma returns them.
+__device__ void final_luma_pair(const Ctx& CA, const Ctx& CB, int modeA, int modeB, bool trel, uint32_t& resA,
+                                uint32_t& resB)
+{
+    [[maybe_unused]] const Ctx& C = CA;  // (the phase counters)
+    WaveLds* W = CA.W;
+    const int l = CA.lane, hm = l >> 5, b = l & 15, bx = b & 3, by = b >> 2;
+    const bool own = (l & 16) == 0;
+    PH_START();
+    build_luma_border(CA);
+    build_luma_border(CB);
+    MbLds* const M = hm ? CB.M : CA.M;
+    const ZwSegment* const S = hm ? CB.S : CA.S;
+    const uint8_t* const sY = hm ? CB.sY : CA.sY;
+    const int mode = hm ? modeB : modeA;
+    const uint8_t* ws = M->ws;
+    const int above = CA.mby != 0, left = CA.mbx != 0;
+    int dcv;
+    {  // DC predictor, per half: its first group the top row, its second the left column
+        const int v = (int)ws[csel(own, 1 + b, (b + 1) * ZW_BPS)] & -(int)(own ? above : left);
+        const int sum = red16(v);
+        const int sa = __builtin_amdgcn_readlane(sum, 0) + __builtin_amdgcn_readlane(sum, 16);
+        const int sb = __builtin_amdgcn_readlane(sum, 32) + __builtin_amdgcn_readlane(sum, 48);
+        const int shf = 3 + above + left;
+        dcv = (!above && !left) ? 128 : (((hm ? sb : sa) + (1 << (shf - 1))) >> shf);
+    }
+    int c[16];
+    uint32_t ppk[4];  // the prediction, a row of 4 pixels per word
+    {
+        const int P0 = ws[0];
+        int L[4], Tp[4], r[16];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            L[i] = ws[(by * 4 + i + 1) * ZW_BPS];
+            Tp[i] = ws[1 + bx * 4 + i];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const uint32_t srow = *(const uint32_t*)(sY + (by * 4 + i) * 16 + bx * 4);
+            ppk[i] = 0;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int p = sel4(mode, dcv, Tp[j], L[i], clamp255(L[i] + Tp[j] - P0));
+                ppk[i] |= (uint32_t)p << (8 * j);
+                r[i * 4 + j] = (int)((srow >> (8 * j)) & 255u) - p;
+            }
+        }
+        fdct16_pk(r, c);
+    }
+    // Y2 (the 16 DCs) in group form, and the simple-quant check (check_all_coeffs_zero)
+    int y2dq;
+    uint32_t anyA, anyB;
+    {
+        const int d = wht_g(c[0], b);
+        const int t = b > 0;
+        const int y2q = quantz(d, S->y2.iq[t], S->y2.bias[t]);
+        if (own) M->lev[16][izz_of(b)] = (int16_t)y2q;
+        y2dq = iwht_g(m24(y2q, (int)S->y2.q[t]), b);
+        int snz = y2q != 0;
+        const uint32_t iq1 = S->y1.iq[1], bs1 = S->y1.bias[1];
+#pragma unroll
+        for (int k = 1; k < 16; k++) snz |= quantz(c[k], iq1, bs1) != 0;
+        const unsigned long long any = __ballot(snz != 0);
+        anyA = (uint32_t)any != 0u;
+        anyB = (uint32_t)(any >> 32) != 0u;
+    }
+    PH_MARK_L(16, l, 0);
+    const int q1 = (int)S->y1.q[1];
+    int nzb = 0;
+    // a block's levels (zigzag, lv[1..15]) to C.M->lev[b], dequantised, inverse
+    // transformed and added to the prediction in C.M->ws
+    auto finish = [&](bool act, int* lv) {
+        wsync();
+        if (act) {
+            int dq[16];
+            lv[0] = 0;
+#pragma unroll
+            for (int n = 0; n < 16; n++) M->lev[b][n] = (int16_t)lv[n];
+#pragma unroll
+            for (int n = 1; n < 16; n++) dq[kZZ(n)] = m24(lv[n], q1);
+            dq[0] = y2dq;
+            idct16(dq);
+            uint8_t* wsp = M->ws;
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                const int y = by * 4 + (k >> 2), x = bx * 4 + (k & 3);
+                const int p = (int)((ppk[k >> 2] >> (8 * (k & 3))) & 255u);
+                wsp[(y + 1) * ZW_BPS + 1 + x] = (uint8_t)clamp255(p + dq[k]);
+            }
+        }
+    };
+    if (trel) {
+        const bool tzl = pf_trivial(c, (uint32_t)q1, S->y1.iq[1], S->sharpen);
+        const unsigned long long tzb = __ballot(tzl);
+        const unsigned tzA = (unsigned)tzb & 0xffffu, tzB = (unsigned)(tzb >> 32) & 0xffffu;
+        // the MBs' edge flags (the MBs above and to the left are final)
+        unsigned eA = 0, eB = 0;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            eA |= (unsigned)(__builtin_amdgcn_readfirstlane(CA.top_c[CA.ocx + 1 + q]) != 0) << q;
+            eA |= (unsigned)(__builtin_amdgcn_readfirstlane(CA.M->left_c[1 + q]) != 0) << (4 + q);
+            eB |= (unsigned)(__builtin_amdgcn_readfirstlane(CB.top_c[CB.ocx + 1 + q]) != 0) << q;
+            eB |= (unsigned)(__builtin_amdgcn_readfirstlane(CB.M->left_c[1 + q]) != 0) << (4 + q);
+        }
+        // the MBs' tasks: bit cx * 16 + b
+        unsigned long long mA = 0, mB = 0;
+        {
+            const unsigned need = pf_need(b, hm ? tzB : tzA, hm ? eB : eA);
+#pragma unroll
+            for (int cx = 0; cx < 3; cx++) {
+                const unsigned long long nb = __ballot((need >> cx) & 1u);
+                mA |= (nb & 0xffffull) << (16 * cx);
+                mB |= ((nb >> 32) & 0xffffull) << (16 * cx);
+            }
+        }
+        const bool one = pf_one_call(mA, mB);
+        // the coefficients to the task lanes (i16 pairs, natural order)
+        if (own) {
+            uint32_t* st = (uint32_t*)M->lev[b];
+#pragma unroll
+            for (int i = 0; i < 8; i++) st[i] = pack_lo(c[2 * i], c[2 * i + 1]);
+        }
+        if (one) PH_COUNT(24);
+        else PH_COUNT(25);
+        const int ncall = one ? 1 : 2;
+#pragma nounroll
+        for (int r = 0; r < ncall; r++) {
+            // this call's tasks per frame, frame 1's numbered after frame 0's
+            const unsigned long long cA = one ? mA : (r == 0 ? ZW_PF_ALL : 0ull);
+            const unsigned long long cB = one ? mB : (r == 1 ? ZW_PF_ALL : 0ull);
+            const int nA = pf_count(cA), nT = nA + pf_count(cB);
+            const unsigned long long cm = hm ? cB : cA;
+            const int base = hm ? nA : 0;
+            if (own) {
+#pragma unroll
+                for (int cx = 0; cx < 3; cx++)
+                    if ((cm >> (cx * 16 + b)) & 1ull) W->dc[pf_task(cm, base, b, cx) & 63] = (hm << 6) | (cx << 4) | b;
+            }
+            wsync();
+            int lv[16];
+#pragma unroll
+            for (int n = 0; n < 16; n++) lv[n] = 0;
+            int tnz = 0;
+            if (l < nT) {
+                const int td = W->dc[l];
+                const bool tf = (td >> 6) & 1;
+                const ZwSegment* const St = tf ? CB.S : CA.S;
+                const uint32_t* st = (const uint32_t*)(tf ? CB.M : CA.M)->lev[td & 15];
+                int dq[16];
+#pragma unroll
+                for (int i = 0; i < 8; i++) {
+                    const uint32_t w = st[i];
+                    dq[2 * i] = lo16(w);
+                    dq[2 * i + 1] = hi16(w);
+                }
+                tnz = trellis<1, true>(dq, lv, St->y1, St->sharpen, St->lt_i16, tf ? CB.T : CA.T, 0, (td >> 4) & 3);
+            }
+            PH_MARK_L(17, l, 0);
+            const unsigned long long nzm = __ballot(l < nT && tnz);
+            // the raster-order context chain of a frame worked in this call, on
+            // the scalar unit: code = the blocks' contexts (2 bits each)
+            auto chain = [&](unsigned long long cmf, int basef, unsigned tz, unsigned e, unsigned& code,
+                             unsigned& nzbits) {
+                int nt[4], nl[4];
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    nt[q] = (int)((e >> q) & 1u);
+                    nl[q] = (int)((e >> (4 + q)) & 1u);
+                }
+                code = nzbits = 0;
+#pragma unroll
+                for (int bb = 0; bb < 16; bb++) {
+                    const int cx = min(nl[bb >> 2] + nt[bb & 3], 2);
+                    const int z = ((tz >> bb) & 1u) ? 0 : (int)((nzm >> (pf_task(cmf, basef, bb, cx) & 63)) & 1ull);
+                    nt[bb & 3] = z;
+                    nl[bb >> 2] = z;
+                    code |= (unsigned)cx << (2 * bb);
+                    nzbits |= (unsigned)z << bb;
+                }
+            };
+            unsigned codeA = 0, nzA = 0, codeB = 0, nzB = 0;
+            if (one || r == 0) chain(cA, 0, tzA, eA, codeA, nzA);
+            if (one || r == 1) chain(cB, nA, tzB, eB, codeB, nzB);
+            const int cxb = (int)(((hm ? codeB : codeA) >> (2 * b)) & 3u);
+            const int srcl = pf_task(cm, base, b, cxb) & 63;
+            // gather the chosen context's levels as i16 pairs (|level| <= 2047)
+            const bool act = own && (one || r == hm);
+            const bool zero = (((hm ? tzB : tzA) >> b) & 1u) != 0u;
+            int gl[16];
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                const uint32_t w = (uint32_t)__shfl((int)pack_lo(lv[2 * i], lv[2 * i + 1]), srcl);
+                gl[2 * i] = zero ? 0 : lo16(w);
+                gl[2 * i + 1] = zero ? 0 : hi16(w);
+            }
+            if (act) nzb = (int)(((hm ? nzB : nzA) >> b) & 1u);
+            PH_MARK_L(18, l, 0);
+            finish(act, gl);
+            wsync();
+        }
+    } else {
+        int lv[16];
+#pragma unroll
+        for (int n = 1; n < 16; n++) {
+            lv[n] = quantz(c[kZZ(n)], S->y1.iq[1], S->y1.bias[1]);
+            nzb |= lv[n] != 0;
+        }
+        finish(own, lv);
+    }
+    const unsigned long long nzall = __ballot(own && nzb);
+    resA = ((uint32_t)nzall & 0xffffu) | (anyA << 16);
+    resB = ((uint32_t)(nzall >> 32) & 0xffffu) | (anyB << 16);
+    wsync();
+    PH_MARK_L(14, l, 0);
+}
+
 // Final chroma transform with error diffusion (transform_chroma_blocks
 // vp8.rs:3039, apply_chroma_error_diffusion :572), lane-pair form: lanes b and
 // 32 + b work block b (U 0..3, V 4..7) from the coefficients pick_uv left for
@@ -3084,11 +3319,11 @@ __device__ __forceinline__ void encode_body(const EncArgs& a)
     const bool keep_i4 = !trel && (PASS == 1 || a.dbg == nullptr);
     const size_t nmb = (size_t)mbw * mbh;
 #ifdef ZW_PHASE_PROF
-    if (lane < 24) W->ph[lane] = 0;
+    if (lane < ZW_PH_N) W->ph[lane] = 0;
     wsync();
     auto ph_flush = [&]() {
-        if (lane < 24) atomicAdd(&zw_phase_cycles_dev[PASS - 1][lane], W->ph[lane]);
-        if (lane < 24) atomicAdd(&zw_wave_cycles_dev[PASS - 1][wv][lane], W->ph[lane]);
+        if (lane < ZW_PH_N) atomicAdd(&zw_phase_cycles_dev[PASS - 1][lane], W->ph[lane]);
+        if (lane < ZW_PH_N) atomicAdd(&zw_wave_cycles_dev[PASS - 1][wv][lane], W->ph[lane]);
     };
 #else
     auto ph_flush = []() {};
@@ -3236,18 +3471,36 @@ __device__ __forceinline__ void encode_body(const EncArgs& a)
         C.top_c = W->win_c;
         C.top_derr = W->win_d;
     }
-    // everything of an MB after its searches: the final transforms, the
-    // complexity contexts (pass 2), the levels, the MB record and the borders
-    auto mb_store = [&](Ctx& C, int lm, int cm, bool i4reuse, uint32_t i4nz, bool trel) __attribute__((always_inline)) {
-        const int lane = C.lane;
-        PH_START();
+    // Everything of an MB after its searches, in three steps: the final luma
+    // transform, the final chroma transform (pass 2), and the stores.  What the
+    // transforms hand on is one word each: the blocks' has-coefficients flags
+    // (luma bits 0..15, chroma bits 0..7) and above them the simple-quant "any
+    // nonzero" flag (luma bit 16, chroma bit 8).
+    auto mb_luma = [&](Ctx& C, int lm, bool i4reuse, uint32_t i4nz, bool trel) __attribute__((always_inline)) {
         int ynz[16];
-        const int lnz = final_luma(C, lm, trel, ynz, i4reuse ? (int)i4nz : -1);
-        PH_MARK(4);
-        int uvnz[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        int cnz = 0;
-        if (PASS == 2) cnz = final_chroma(C, cm, C.top_derr + C.od, uvnz);
-        PH_MARK(5);
+        uint32_t r = (uint32_t)(final_luma(C, lm, trel, ynz, i4reuse ? (int)i4nz : -1) != 0) << 16;
+#pragma unroll
+        for (int k = 0; k < 16; k++) r |= (uint32_t)(ynz[k] != 0) << k;
+        return r;
+    };
+    auto mb_chroma = [&](Ctx& C, int cm) __attribute__((always_inline)) {
+        int uvnz[8];
+        uint32_t r = (uint32_t)(final_chroma(C, cm, C.top_derr + C.od, uvnz) != 0) << 8;
+#pragma unroll
+        for (int k = 0; k < 8; k++) r |= (uint32_t)(uvnz[k] != 0) << k;
+        return r;
+    };
+    // the stores: the complexity contexts (pass 2), the levels, the MB record
+    // and the borders (the chroma borders only if the caller has not stored them)
+    auto mb_finish = [&](Ctx& C, int lm, int cm, uint32_t lres, uint32_t cres, bool chroma_borders)
+                         __attribute__((always_inline)) {
+        const int lane = C.lane;
+        int ynz[16], uvnz[8];
+#pragma unroll
+        for (int k = 0; k < 16; k++) ynz[k] = (int)((lres >> k) & 1u);
+#pragma unroll
+        for (int k = 0; k < 8; k++) uvnz[k] = (int)((cres >> k) & 1u);
+        const int lnz = (int)((lres >> 16) & 1u), cnz = (int)((cres >> 8) & 1u);
         ZwMbOut* o = a.out + (size_t)C.f * nmb + (size_t)C.mby * mbw + C.mbx;
         if (PASS == 2) {
             const int skip = !(lnz | cnz);
@@ -3278,7 +3531,7 @@ __device__ __forceinline__ void encode_body(const EncArgs& a)
                 o->skip = (uint8_t)skip;
                 o->chroma_mode = (uint8_t)cm;
             }
-            store_chroma_borders(C);
+            if (chroma_borders) store_chroma_borders(C);
             write_levels(C, 0, 25, skip);
             if (a.sizes) {
                 // the packed record size k_pack_size would compute from these
@@ -3308,6 +3561,15 @@ __device__ __forceinline__ void encode_body(const EncArgs& a)
         }
         if (lane < 16) o->bpred[lane] = lm == 4 ? C.M->modes[lane] : 0;
         store_luma_borders(C);
+    };
+    auto mb_store = [&](Ctx& C, int lm, int cm, bool i4reuse, uint32_t i4nz, bool trel) __attribute__((always_inline)) {
+        [[maybe_unused]] const int lane = C.lane;
+        PH_START();
+        const uint32_t lres = mb_luma(C, lm, i4reuse, i4nz, trel);
+        PH_MARK(4);
+        const uint32_t cres = PASS == 2 ? mb_chroma(C, cm) : 0u;
+        PH_MARK(5);
+        mb_finish(C, lm, cm, lres, cres, true);
     };
     if constexpr (PAIR) {
         // ---- frame pairs: every wave works MB row y of both frames of the
@@ -3443,24 +3705,87 @@ ZW_PAIR_LOOP
                 }
                 wsync();
                 PH_MARK(2);
+                // The final stage.  Chroma first, frame by frame (pass 2; in pass 1
+                // the chain waves work it): W->uvc, cu and cv are the wave's, so a
+                // frame's final chroma and chroma borders are done before the other
+                // frame's search.  Its result replaces the I16 score in W->pst.
+                if (PASS == 2) {
+ZW_PAIR_LOOP
+                    for (int fr = 0; fr < 2; fr++) {
+                        if (fr >= nf) continue;
+                        enter(fr);
+                        C.seg = (int)(pst(fr, 0) >> 8);
+                        C.S = C.Sl + C.seg;
+                        build_chroma_border(C);
+                        const int cm = pick_uv<PASS>(C);
+                        PH_MARK(3);
+                        const uint32_t cres = mb_chroma(C, cm);
+                        store_chroma_borders(C);
+                        if (lane == 0) W->pst[fr][1] = cres | ((uint32_t)cm << 9);
+                        PH_MARK(5);
+                    }
+                }
+                // Luma: two I16 MBs in one pass of the wave (final_luma_pair),
+                // anything else (an I4 MB, the odd last workgroup, frames whose
+                // trellis settings differ) frame by frame.
+                const uint32_t w0 = pst(0, 3), w1 = pst(1, 3);
+                if (nf == 2 && !((w0 | w1) & 0x10000u) && trel == trel1) {
+                    Ctx CA = C, CB = C;
+                    CA.lane = CB.lane = opaque_lane(threadIdx.x & 63);
+                    CA.f = f;
+                    CB.f = f + 1;
+                    CA.T = T;
+                    CB.T = (const LdsTables*)((const uint8_t*)T + L.sT);
+                    CA.M = Mp[0];
+                    CB.M = Mp[1];
+                    CA.S = Sl + (s0 >> 8);
+                    CB.S = (const ZwSegment*)((const uint8_t*)Sl + L.sS) + (s1 >> 8);
+                    CA.sY = Mp[0]->sy;
+                    CB.sY = Mp[1]->sy;
+                    CA.top_y = top_y;
+                    CB.top_y = top_y + L.sy;
+                    CA.top_c = top_c;
+                    CB.top_c = top_c + L.sc;
+                    CA.mbx = CB.mbx = mbx;
+                    CA.mby = CB.mby = mby;
+                    CA.oy = CB.oy = mbx * 16;
+                    CA.ocx = CB.ocx = mbx * 12;
+                    uint32_t r0, r1;
+                    final_luma_pair(CA, CB, (int)(s0 & 15u), (int)(s1 & 15u), trel, r0, r1);
+                    if (lane == 0) {
+                        W->pst[0][2] = r0;
+                        W->pst[1][2] = r1;
+                    }
+                } else {
+ZW_PAIR_LOOP
+                    for (int fr = 0; fr < 2; fr++) {
+                        if (fr >= nf) continue;
+                        enter(fr);
+                        const uint32_t sm = pst(fr, 0), r4 = pst(fr, 3);
+                        C.seg = (int)(sm >> 8);
+                        C.S = C.Sl + C.seg;
+                        const bool w4 = (r4 >> 16) & 1u;
+                        const uint32_t lres = mb_luma(C, w4 ? 4 : (int)(sm & 15u), w4 && (fr ? keep1 : keep_i4),
+                                                      r4 & 0xffffu, fr ? trel1 : trel);
+                        if (lane == 0) W->pst[fr][2] = lres;
+                    }
+                    if (nf == 2) PH_COUNT(26);
+                }
+                wsync();
+                PH_MARK(4);
+                // the stores, frame by frame
 ZW_PAIR_LOOP
                 for (int fr = 0; fr < 2; fr++) {
                     if (fr >= nf) continue;
                     enter(fr);
-                    const uint32_t sm = pst(fr, 0), r4 = pst(fr, 3);
+                    const uint32_t sm = pst(fr, 0), r4 = pst(fr, 3), cr = pst(fr, 1);
                     C.seg = (int)(sm >> 8);
                     C.S = C.Sl + C.seg;
-                    int cm = 0;  // (pass 1: the chain waves work the chroma)
-                    if (PASS == 2) {
-                        build_chroma_border(C);
-                        cm = pick_uv<PASS>(C);
-                    }
-                    PH_MARK(3);
                     const bool w4 = (r4 >> 16) & 1u;
-                    mb_store(C, w4 ? 4 : (int)(sm & 15u), cm, w4 && (fr ? keep1 : keep_i4), r4 & 0xffffu,
-                             fr ? trel1 : trel);
-                    PH_RESET();
+                    mb_finish(C, w4 ? 4 : (int)(sm & 15u), PASS == 2 ? (int)(cr >> 9) : 0, pst(fr, 2),
+                              PASS == 2 ? cr & 0x1ffu : 0u, false);
                 }
+                PH_RESET();
                 publish(progress, wv, mby * 65536 + mbx + 1);
                 PH_MARK(6);
             }

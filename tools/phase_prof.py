@@ -26,7 +26,10 @@ NAMES = {0: "wait(row above)", 1: "border+pick_i16", 2: "pick_i4", 3: "pick_uv",
          16: "    i16: fdct+y2", 17: "    i16: quant check+trellis", 18: "    i16: ctx resolve+gather",
          19: "  (I4 search steps run)", 20: "  (I4 searches)",
          21: "wait(above-right)+border",
-         22: "  i4q: modes+pred+src", 23: "  i4q: fdct+quant+cost"}
+         22: "  i4q: modes+pred+src", 23: "  i4q: fdct+quant+cost",
+         24: "  (pairs: one trellis call)", 25: "  (pairs: a call per frame)", 26: "  (pairs: per-frame final)"}
+NPH = 28  # ZW_PH_N (zw_enc_kernels.hip)
+COUNTS = (7, 19, 20, 24, 25, 26)
 
 
 def main():
@@ -36,7 +39,7 @@ def main():
     m = int(sys.argv[4]) if len(sys.argv) > 4 else 4
     L = zwebp.load_library()
     L.zw_phase_cycles.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    buf = (ctypes.c_ulonglong * 48)()
+    buf = (ctypes.c_ulonglong * (2 * NPH))()
     p = zwebp.Pipeline(F, w, h, zwebp.ColorType.Rgba8, 75, m)
     imgs = [synth_rgba(w, h, 0x5EED0000 + i) for i in range(4)]
     for i in range(F):
@@ -48,24 +51,24 @@ def main():
     el = time.perf_counter() - t
     assert L.zw_phase_cycles(buf, 0) == 0
     L.zw_wave_cycles.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    wbuf = (ctypes.c_ulonglong * (2 * 16 * 24))()
+    wbuf = (ctypes.c_ulonglong * (2 * 16 * NPH))()
     assert L.zw_wave_cycles(wbuf, 0) == 0
     kt = p.kernel_times()
     nmb = p.mbw * p.mbh * F
     print(f"{F} frames {w}x{h} m{m}: step {el * 1e3:.1f} ms, kernels(ms) {[round(x, 2) for x in kt[:4]]} "
           f"host(ms) fetch1/stats/fetch2/emit {[round(x, 2) for x in kt[4:8]]}")
     for ps in (0, 1):
-        tot = sum(buf[ps * 24 + k] for k in list(range(10)) + [21] if k not in (7, 19, 20)) or 1
+        tot = sum(buf[ps * NPH + k] for k in list(range(10)) + [21] if k not in COUNTS) or 1
         print(f"pass {ps + 1}: total {tot / 1e9:.2f} G wave-cycles, {tot / nmb:.0f} wave-cycles/MB")
-        for k in range(24):
-            v = buf[ps * 24 + k]
-            if v and k in (7, 19, 20):
+        for k in range(NPH):
+            v = buf[ps * NPH + k]
+            if v and k in COUNTS:
                 print(f"   {NAMES.get(k, k):24s} {v / nmb:12.3f} of MBs")
             elif v:
                 print(f"   {NAMES.get(k, k):24s} {v / nmb:12.0f} cyc/MB  {100 * v / tot:5.1f}%")
         print(f"   per wave (pass {ps + 1}): total G cycles / wait G cycles / MBs(approx by I4 searches)")
         for wv in range(16):
-            b = [wbuf[(ps * 16 + wv) * 24 + k] for k in range(24)]
+            b = [wbuf[(ps * 16 + wv) * NPH + k] for k in range(NPH)]
             t = sum(b[k] for k in list(range(10)) + [21] if k not in (7,))
             if t:
                 print(f"     wave {wv:2d}: {t / 1e9:8.2f}  wait {(b[0] + b[21]) / 1e9:7.2f}  ({100 * (b[0] + b[21]) / t:4.1f}%)"
