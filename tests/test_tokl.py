@@ -36,7 +36,9 @@ def test_tokl_goldens(path):
     vp8 = open(path, "rb").read()
     rc, match = zwebp.dbg_tokl_frame(vp8)
     one_column = ((vp8[6] | vp8[7] << 8) & 0x3FFF) <= 16  # (parsed on the host only)
-    assert rc == 0 and match == (-1 if one_column else 1)
+    rc_hdr, hdr = O.decode_header(vp8)
+    assert rc_hdr == 0
+    assert rc == 0 and match == (-1 if one_column or hdr.num_partitions > 1 else 1)  # (several partitions: too)
 
 
 @pytest.mark.parametrize("q", [0, 5, 20, 50, 75, 90, 100])

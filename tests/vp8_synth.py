@@ -1,0 +1,450 @@
+"""A VP8 key-frame writer for tests (RFC 6386) -- TEST INFRASTRUCTURE ONLY.
+
+No encoder at hand can be told to emit most of what the frame header allows
+(loop-filter deltas, sharpness, quantiser deltas, delta-mode segment values, a
+segment map that is not updated, an absent skip flag ...), so the streams that
+take those decoder paths are written here directly, from a plain dict of header
+fields and a list of macroblocks.
+
+  BoolEncoder      RFC 6386 s7, kept as one big integer so that carries need no
+                   special case (not the byte-wise form of oracle/or_enc.c: a
+                   shared bug must not hide; tests/test_synth_streams.py checks
+                   the two byte for byte)
+  write_keyframe   params + mbs -> the 'VP8 ' payload
+  random_mbs       uniform modes on every MB, heavy-tailed levels
+  default_params   a header with nothing optional in it
+
+`params` (every field of the first partition's header, s9.2-9.11, s19.2):
+  width, height
+  segments      None, or {update_map, update_data, absolute, quant[4], lf[4],
+                map_probs[3]}; quant/lf entries are ints or None (flag 0, value
+                0), map_probs entries ints or None (255)
+  filter_type (1 = simple), filter_level, sharpness
+  lf_delta      None, or {update, ref[4], mode[4]} (entries int or None)
+  log2_nparts
+  yac, ydc_delta, y2dc_delta, y2ac_delta, uvdc_delta, uvac_delta (int or None)
+  coeff_probs   [] or 1056 entries in [i][j][k][t] order, -1 = not updated
+  skip_prob     int, or None for an absent skip flag
+`mbs`: per MB in raster order a dict of segment, skip, ymode (0 DC, 1 V, 2 H,
+  3 TM, 4 B), bmodes[16] (0 DC, 1 TM, 2 VE, 3 HE, 4 LD, 5 RD, 6 VR, 7 VL, 8 HD,
+  9 HU), uvmode, levels[25][16] (blocks 0-15 Y, 16-19 U, 20-23 V, 24 Y2; signed
+  levels in zigzag scan order).
+"""
+import ctypes
+import hashlib
+import os
+import re
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _tables(path):
+    """ZW_TABLE(ctype, NAME, [d0][d1].., values) entries of a tables .inc file."""
+    out = {}
+    text = open(path).read()
+    for m in re.finditer(r"ZW_TABLE\(\s*\w+\s*,\s*(\w+)\s*,\s*((?:\[\d+\])+)\s*,([^)]*)\)", text):
+        dims = [int(d) for d in re.findall(r"\d+", m.group(2))]
+        vals = [int(v) for v in re.findall(r"-?\d+", m.group(3))]
+        out[m.group(1)] = np.array(vals, np.int64).reshape(dims)
+    return out
+
+
+_K = _tables(os.path.join(ROOT, "oracle", "or_tables.inc"))  # the key-frame mode contexts
+_T = _tables(os.path.join(ROOT, "image-webp_amd", "csrc", "zw_tables.inc"))  # the token tables
+YMODE_PROBS, BMODE_PROBS, UVMODE_PROBS = (_K[n] for n in ("KEYFRAME_YMODE_PROBS", "KEYFRAME_BPRED_MODE_PROBS",
+                                                             "KEYFRAME_UV_MODE_PROBS"))
+COEFF_PROBS, COEFF_UPDATE_PROBS, PROB_DCT_CAT, COEFF_BANDS, DC_QUANT, AC_QUANT = (
+    _T[n] for n in ("COEFF_PROBS", "COEFF_UPDATE_PROBS", "PROB_DCT_CAT", "COEFF_BANDS", "DC_QUANT", "AC_QUANT"))
+
+# RFC 6386 s8.1, s9.3, s11.2, s13.2: trees as arrays, leaves as -value.  The
+# leaf -0 cannot be told from the index 0, which no branch points back to.
+SEGMENT_TREE = (2, 4, -0, -1, -2, -3)
+YMODE_TREE = (-4, 2, 4, 6, -0, -1, -2, -3)
+UVMODE_TREE = (-0, 2, -1, 4, -2, -3)
+BMODE_TREE = (-0, 2, -1, 4, -2, 6, 8, 12, -3, 10, -5, -6, -4, 14, -7, 16, -8, -9)
+B_PRED = 4
+INTRA_OF_YMODE = (0, 2, 3, 1)  # the sub-block mode an I16 MB stands for as a context: DC, VE, HE, TM
+
+
+def _paths(tree):
+    """value -> [(probability index, bit), ...] from the root."""
+    out = {}
+
+    def walk(i, path):
+        for bit in (0, 1):
+            t = tree[i + bit]
+            if t > 0:
+                walk(t, path + [(i >> 1, bit)])
+            else:
+                out[-t] = path + [(i >> 1, bit)]
+    walk(0, [])
+    return out
+
+
+_SEG_PATH, _YMODE_PATH, _UV_PATH, _BMODE_PATH = (_paths(t) for t in (SEGMENT_TREE, YMODE_TREE, UVMODE_TREE, BMODE_TREE))
+
+
+class BoolEncoder:
+    """RFC 6386 s7.3.  `low` is the whole code value so far, an integer of
+    8 + shifts bits; an addition carries through it like through any integer."""
+
+    def __init__(self):
+        self.low, self.range, self.shifts = 0, 255, 0
+
+    def put(self, bit, prob):
+        split = 1 + (((self.range - 1) * int(prob)) >> 8)
+        if bit:
+            self.low += split
+            self.range -= split
+        else:
+            self.range = split
+        n = 8 - self.range.bit_length()  # until 128 <= range
+        if n > 0:
+            self.range <<= n
+            self.low <<= n
+            self.shifts += n
+
+    def lit(self, nbits, value):
+        for b in range(nbits - 1, -1, -1):
+            self.put((value >> b) & 1, 128)
+
+    def flag(self, f):
+        self.put(1 if f else 0, 128)
+
+    def signed(self, nbits, value):
+        """A flagged magnitude-and-sign field (s9.3, s9.6); None = flag 0."""
+        self.flag(value is not None)
+        if value is not None:
+            self.lit(nbits, abs(value))
+            self.flag(value < 0)
+
+    def tree(self, path, probs):
+        for pi, bit in path:
+            self.put(bit, int(probs[pi]))
+
+    def finish(self):
+        """The bytes the RFC's encoder has written after its flush: one per 8
+        shifts from the 24th on, then the 32-bit `bottom` left-aligned."""
+        nbytes = 4 + (0 if self.shifts < 24 else 1 + (self.shifts - 24) // 8)
+        return (self.low << (8 * nbytes - 8 - self.shifts)).to_bytes(nbytes, "big")
+
+
+def default_params(width, height):
+    return dict(width=width, height=height, segments=None, filter_type=0, filter_level=0, sharpness=0, lf_delta=None,
+                log2_nparts=0, yac=40, ydc_delta=None, y2dc_delta=None, y2ac_delta=None, uvdc_delta=None,
+                uvac_delta=None, coeff_probs=[], skip_prob=None)
+
+
+def quant_indices(params):
+    """Per segment the base quantiser index before clamping (s9.6, s9.3)."""
+    seg = params["segments"]
+    if not seg:
+        return [params["yac"]] * 4
+    q = [(v or 0) for v in seg["quant"]] if seg["update_data"] else [0] * 4
+    if seg["update_data"] and not seg["absolute"]:
+        q = [v + params["yac"] for v in q]
+    return q
+
+
+def dequant_factors(params):
+    """Per segment (ydc, yac, y2dc, y2ac, uvdc, uvac), s14.1."""
+    def at(tab, i):
+        return int(tab[min(max(i, 0), 127)])
+    out = []
+    for base in quant_indices(params):
+        d = [(params[k] or 0) for k in ("ydc_delta", "y2dc_delta", "y2ac_delta", "uvdc_delta", "uvac_delta")]
+        out.append((at(DC_QUANT, base + d[0]), at(AC_QUANT, base), 2 * at(DC_QUANT, base + d[1]),
+                    max(at(AC_QUANT, base + d[2]) * 155 // 100, 8), min(at(DC_QUANT, base + d[3]), 132),
+                    at(AC_QUANT, base + d[4])))
+    return out
+
+
+def _write_header(e, p):
+    e.lit(1, 0)  # colour space
+    e.lit(1, 0)  # clamping type
+    seg = p["segments"]
+    e.flag(seg is not None)
+    if seg is not None:
+        e.flag(seg["update_map"])
+        e.flag(seg["update_data"])
+        if seg["update_data"]:
+            e.flag(seg["absolute"])
+            for v in seg["quant"]:
+                e.signed(7, v)
+            for v in seg["lf"]:
+                e.signed(6, v)
+        if seg["update_map"]:
+            for v in seg["map_probs"]:
+                e.flag(v is not None)
+                if v is not None:
+                    e.lit(8, v)
+    e.flag(p["filter_type"])
+    e.lit(6, p["filter_level"])
+    e.lit(3, p["sharpness"])
+    lfd = p["lf_delta"]
+    e.flag(lfd is not None)
+    if lfd is not None:
+        e.flag(lfd["update"])
+        if lfd["update"]:
+            for v in lfd["ref"]:
+                e.signed(6, v)
+            for v in lfd["mode"]:
+                e.signed(6, v)
+    e.lit(2, p["log2_nparts"])
+    e.lit(7, p["yac"])
+    for k in ("ydc_delta", "y2dc_delta", "y2ac_delta", "uvdc_delta", "uvac_delta"):
+        e.signed(4, p[k])
+    e.lit(1, 0)  # refresh_entropy_probs
+    probs = COEFF_PROBS.copy().reshape(-1)
+    upd = p["coeff_probs"] or [-1] * probs.size
+    assert len(upd) == probs.size
+    for n, (u, up) in enumerate(zip(upd, COEFF_UPDATE_PROBS.reshape(-1))):
+        e.put(u >= 0, int(up))
+        if u >= 0:
+            e.lit(8, u)
+            probs[n] = u
+    e.lit(1, p["skip_prob"] is not None)
+    if p["skip_prob"] is not None:
+        e.lit(8, p["skip_prob"])
+    return probs.reshape(COEFF_PROBS.shape)
+
+
+def _write_block(e, P, lv, first, ctx):
+    """One block's tokens (s13.2-13.4); returns whether any was coded before the end."""
+    nzpos = [n for n in range(first, 16) if lv[n]]
+    last = nzpos[-1] if nzpos else -1
+    n = first
+    p = P[COEFF_BANDS[n]][ctx]
+    while n < 16:
+        if n > last:
+            e.put(0, int(p[0]))  # end of block
+            break
+        e.put(1, int(p[0]))
+        while not lv[n]:
+            e.put(0, int(p[1]))  # a zero; no end-of-block test follows it
+            n += 1
+            p = P[COEFF_BANDS[n]][0]
+        e.put(1, int(p[1]))
+        v = abs(int(lv[n]))
+        if v == 1:
+            e.put(0, int(p[2]))
+            nctx = 1
+        else:
+            e.put(1, int(p[2]))
+            nctx = 2
+            if v <= 4:
+                e.put(0, int(p[3]))
+                e.put(v > 2, int(p[4]))
+                if v > 2:
+                    e.put(v == 4, int(p[5]))
+            elif v <= 10:
+                e.put(1, int(p[3]))
+                e.put(0, int(p[6]))
+                e.put(v > 6, int(p[7]))
+                if v <= 6:
+                    e.put(v == 6, 159)
+                else:
+                    e.put(v >= 9, 165)
+                    e.put((v - 7) & 1, 145)
+            else:
+                e.put(1, int(p[3]))
+                e.put(1, int(p[6]))
+                cat = 0  # 0..3 = DCT categories 3..6: 11-18, 19-34, 35-66, 67-2114
+                while cat < 3 and v >= 3 + (16 << cat):
+                    cat += 1
+                e.put(cat >> 1, int(p[8]))
+                e.put(cat & 1, int(p[9 + (cat >> 1)]))
+                cp = [int(c) for c in PROB_DCT_CAT[2 + cat] if c]
+                extra = v - 3 - (8 << cat)
+                assert 0 <= extra < (1 << len(cp)), v
+                for k, c in enumerate(cp):
+                    e.put((extra >> (len(cp) - 1 - k)) & 1, c)
+        e.put(lv[n] < 0, 128)
+        n += 1
+        if n < 16:
+            p = P[COEFF_BANDS[n]][nctx]
+    return 1 if last >= first else 0
+
+
+def write_keyframe(params, mbs):
+    p = params
+    mbw, mbh = (p["width"] + 15) // 16, (p["height"] + 15) // 16
+    assert len(mbs) == mbw * mbh
+    nparts = 1 << p["log2_nparts"]
+    hdr = BoolEncoder()
+    parts = [BoolEncoder() for _ in range(nparts)]
+    P = _write_header(hdr, p)
+    seg = p["segments"]
+    seg_probs = [255 if v is None else v for v in seg["map_probs"]] if seg and seg["update_map"] else None
+    top_bp = np.zeros((mbw, 4), np.int64)
+    top_cx = np.zeros((mbw, 9), np.int64)  # 0 Y2, 1-4 Y, 5-6 U, 7-8 V
+    for mby in range(mbh):
+        e = parts[mby % nparts]
+        left_bp = [0] * 4
+        left_cx = [0] * 9
+        for mbx in range(mbw):
+            mb = mbs[mby * mbw + mbx]
+            ym = mb["ymode"]
+            if seg_probs is not None:
+                hdr.tree(_SEG_PATH[mb["segment"]], seg_probs)
+            else:
+                assert mb["segment"] == 0
+            skip = bool(mb["skip"])
+            if p["skip_prob"] is not None:
+                hdr.put(skip, p["skip_prob"])
+            else:
+                assert not skip
+            hdr.tree(_YMODE_PATH[ym], YMODE_PROBS)
+            if ym == B_PRED:
+                for y in range(4):
+                    for x in range(4):
+                        m = mb["bmodes"][x + 4 * y]
+                        hdr.tree(_BMODE_PATH[m], BMODE_PROBS[top_bp[mbx][x]][left_bp[y]])
+                        top_bp[mbx][x] = left_bp[y] = m
+            else:
+                top_bp[mbx][:] = INTRA_OF_YMODE[ym]
+                left_bp = [INTRA_OF_YMODE[ym]] * 4
+            hdr.tree(_UV_PATH[mb["uvmode"]], UVMODE_PROBS)
+            tcx = top_cx[mbx]
+            if skip:  # s13: no tokens; the contexts clear, Y2's only where the MB has a Y2
+                keep = (tcx[0], left_cx[0])
+                tcx[:] = 0
+                left_cx = [0] * 9
+                if ym == B_PRED:
+                    tcx[0], left_cx[0] = keep
+                continue
+            lv = mb["levels"]
+            first = 0
+            if ym != B_PRED:
+                tcx[0] = left_cx[0] = _write_block(e, P[1], lv[24], 0, tcx[0] + left_cx[0])
+                first = 1
+            for y in range(4):
+                for x in range(4):
+                    nz = _write_block(e, P[0 if first else 3], lv[x + 4 * y], first, tcx[1 + x] + left_cx[1 + y])
+                    tcx[1 + x] = left_cx[1 + y] = nz
+            for base, c0 in ((16, 5), (20, 7)):
+                for y in range(2):
+                    for x in range(2):
+                        nz = _write_block(e, P[2], lv[base + x + 2 * y], 0, tcx[c0 + x] + left_cx[c0 + y])
+                        tcx[c0 + x] = left_cx[c0 + y] = nz
+    first_part = hdr.finish()
+    bodies = [e.finish() for e in parts]
+    assert len(first_part) < (1 << 19)
+    tag = (len(first_part) << 5) | (1 << 4)  # key frame, version 0, shown
+    out = bytearray(tag.to_bytes(3, "little") + b"\x9d\x01\x2a")
+    out += p["width"].to_bytes(2, "little") + p["height"].to_bytes(2, "little")  # (no scaling)
+    out += first_part
+    for b in bodies[:-1]:
+        out += len(b).to_bytes(3, "little")
+    for b in bodies:
+        out += b
+    return bytes(out)
+
+
+LEVEL_BUDGET = 2047  # per block, sum of |level * dequantiser| (so each product stays within it too)
+
+
+def _magnitude(rng):
+    u = rng.random()
+    if u < 0.50:
+        return 1
+    if u < 0.70:
+        return 2
+    if u < 0.80:
+        return int(rng.integers(3, 5))
+    if u < 0.86:
+        return int(rng.integers(5, 7))
+    if u < 0.91:
+        return int(rng.integers(7, 11))
+    cat = int(rng.integers(0, 4))  # DCT categories 3..6, each as likely
+    return 3 + (8 << cat) + int(rng.integers(0, 2048 if cat == 3 else (8 << cat)))
+
+
+def random_mbs(params, seed, density=0.35, skip_frac=0.25, empty_frac=0.12):
+    """Modes uniform (every mode on every frame edge), levels with a heavy tail
+    (DCT categories 3-6 occur wherever the quantiser leaves room), capped so that
+    a block's sum of |level * dequantiser| stays within LEVEL_BUDGET: no
+    conforming encoder goes past 2047 for one coefficient, and beyond it the
+    inverse transforms of different decoders need not agree.  A skipped MB
+    carries no levels; some MBs that are not skipped carry none either."""
+    rng = np.random.default_rng(seed)
+    mbw, mbh = (params["width"] + 15) // 16, (params["height"] + 15) // 16
+    seg = params["segments"]
+    dq = dequant_factors(params)
+    mbs = []
+    for _ in range(mbw * mbh):
+        segment = int(rng.integers(0, 4)) if seg and seg["update_map"] else 0
+        ymode = int(rng.integers(0, 5))
+        bmodes = [int(v) for v in rng.integers(0, 10, 16)]
+        uvmode = int(rng.integers(0, 4))
+        skip = int(params["skip_prob"] is not None and rng.random() < skip_frac)
+        empty = rng.random() < empty_frac
+        levels = np.zeros((25, 16), np.int64)
+        ydc, yac, y2dc, y2ac, uvdc, uvac = dq[segment]
+        for b in range(25):
+            dc, ac = (ydc, yac) if b < 16 else ((uvdc, uvac) if b < 24 else (y2dc, y2ac))
+            first = 1 if (b < 16 and ymode != B_PRED) else 0
+            blank = rng.random() < 0.2
+            vals = [(_magnitude(rng), rng.random(), rng.random()) for _ in range(16)]  # (drawn whatever happens)
+            if skip or empty or blank or (b == 24 and ymode == B_PRED):
+                continue
+            left = LEVEL_BUDGET
+            for n in range(first, 16):
+                v, u, s = vals[n]
+                if u >= density * (1.0 - n / 24.0):
+                    continue
+                q = dc if n == 0 else ac
+                v = min(v, left // q)
+                left -= v * q
+                levels[b][n] = -v if s < 0.5 else v
+        mbs.append(dict(segment=segment, skip=skip, ymode=ymode, bmodes=bmodes, uvmode=uvmode, levels=levels))
+    return mbs
+
+
+def plane_digests(y, u, v, width, height, y_stride, uv_stride):
+    """SHA-256 of the cropped Y, U and V planes (rows of y_stride / uv_stride bytes)."""
+    cw, ch = (width + 1) // 2, (height + 1) // 2
+    planes = (np.asarray(y).reshape(-1, y_stride)[:height, :width], np.asarray(u).reshape(-1, uv_stride)[:ch, :cw],
+              np.asarray(v).reshape(-1, uv_stride)[:ch, :cw])
+    return [hashlib.sha256(np.ascontiguousarray(pl).tobytes()).hexdigest() for pl in planes]
+
+
+_WEBP = None
+
+
+def libwebp():
+    """The system libwebp, the independent decoder (None where it is absent)."""
+    global _WEBP
+    if _WEBP is None:
+        try:
+            W = ctypes.CDLL("libwebp.so.7")
+        except OSError:
+            _WEBP = False
+            return None
+        W.WebPDecodeYUV.restype = ctypes.c_void_p
+        W.WebPDecodeYUV.argtypes = [ctypes.c_char_p, ctypes.c_size_t] + [ctypes.c_void_p] * 6
+        W.WebPFree.argtypes = [ctypes.c_void_p]
+        _WEBP = W
+    return _WEBP or None
+
+
+def libwebp_yuv_digests(vp8):
+    """WebPDecodeYUV of the payload in a RIFF wrapper -> plane digests, or None if libwebp rejects it."""
+    W = libwebp()
+    body = b"WEBP" + b"VP8 " + len(vp8).to_bytes(4, "little") + vp8 + b"\0" * (len(vp8) & 1)
+    riff = b"RIFF" + len(body).to_bytes(4, "little") + body
+    w, h, ys, uvs = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    u, v = ctypes.c_void_p(), ctypes.c_void_p()
+    y = W.WebPDecodeYUV(riff, len(riff), ctypes.byref(w), ctypes.byref(h), ctypes.byref(u), ctypes.byref(v),
+                        ctypes.byref(ys), ctypes.byref(uvs))
+    if not y:
+        return None
+    ch = (h.value + 1) // 2
+    Y = np.frombuffer((ctypes.c_uint8 * (ys.value * h.value)).from_address(y), np.uint8)
+    U = np.frombuffer((ctypes.c_uint8 * (uvs.value * ch)).from_address(u.value), np.uint8)
+    V = np.frombuffer((ctypes.c_uint8 * (uvs.value * ch)).from_address(v.value), np.uint8)
+    d = plane_digests(Y, U, V, w.value, h.value, ys.value, uvs.value)
+    W.WebPFree(ctypes.c_void_p(y))
+    return d
