@@ -32,11 +32,15 @@
 #include "zw_common.h"
 #include "zw_host_emit.h"
 #include "zw_host_internal.h"
+#include "zw_ingest.h"
 #include "zw_progress.h"
 
 extern "C" {
 hipError_t zwk_rgb2yuv(hipStream_t s, const uint8_t* img, int w, int h, int bpp, int mbw, int mbh, uint8_t* Y,
                        uint8_t* U, uint8_t* V, size_t img_stride, size_t ysz, size_t csz, int nframes);
+hipError_t zwk_rgb2yuv_dev(hipStream_t s, const void* data, int layout, int dtype, int channels, size_t frame_stride,
+                           size_t plane_stride, size_t row_stride, const float* scale, const float* bias, int w, int h,
+                           int mbw, int mbh, uint8_t* Y, uint8_t* U, uint8_t* V, size_t ysz, size_t csz, int nframes);
 hipError_t zwk_analysis(hipStream_t s, const uint8_t* Y, const uint8_t* U, const uint8_t* V, int mbw, int mbh,
                         size_t ysz, size_t csz, uint8_t* alpha, uint32_t* histo, int nframes);
 hipError_t zwk_segments(hipStream_t s, uint32_t* histo, const ZwFrameParams* tmpl, ZwFrameParams* params,
@@ -624,6 +628,9 @@ struct zw_pipe {
     // zw_pipe_encode_host call on the DMA-staging path (ZW_UPLOAD_PACK=0: off)
     bool up_pack = false;
     uint8_t* img_buf(int parity) const { return parity ? d_img2 : d_img; }
+    // zw_pipe_set_input_device: the frames are read from the caller's device
+    // tensor (k_rgb2yuv_dev) instead of d_img; dev_in.data null = the packed buffer
+    zw_device_images dev_in = {};
 };
 
 static void pipe_free(zw_pipe* p)
@@ -837,6 +844,8 @@ extern "C" int zw_pipe_set_container(zw_pipe* p, int enable, const uint8_t* cons
         return ZW_OK;
     }
     const bool has_alpha = p->color == ZW_COLOR_LA8 || p->color == ZW_COLOR_RGBA8;
+    // (the ALPH chunk is coded from host frames; a device tensor's alpha plane is not brought down)
+    if (has_alpha && p->dev_in.data) return ZW_EINVAL;
     if (has_alpha) {
         // encode_alpha_lossless refuses > 16384 (api.rs:1187): InvalidDimensions
         // up front, not a VP8X file with an empty ALPH chunk
@@ -847,6 +856,51 @@ extern "C" int zw_pipe_set_container(zw_pipe* p, int enable, const uint8_t* cons
         p->host_frames.assign(host_frames, host_frames + p->n);
     }
     p->container = true;
+    return ZW_OK;
+}
+
+// A device tensor of n frames of w x h as the encoder's input: layout, dtype
+// and channels, the strides' bounds and the span (ing_span), the element
+// alignment, and that `data` is device memory of the context's device.
+static int check_device_input(zw_ctx* ctx, const zw_device_images* in, int n, uint32_t w, uint32_t h)
+{
+    if (!ctx || !in || !in->data || n <= 0) return ZW_EINVAL;
+    if ((in->layout != ZW_LAYOUT_HWC && in->layout != ZW_LAYOUT_CHW) ||
+        (in->dtype != ZW_DTYPE_U8 && in->dtype != ZW_DTYPE_F16 && in->dtype != ZW_DTYPE_F32) ||
+        (in->channels != 3 && in->channels != 4) || in->upsampling != 0)
+        return ZW_EINVAL;
+    size_t need = 0, bytes = 0;
+    if (!ing_span(in->layout, (size_t)n, w, h, (size_t)in->channels, in->frame_stride, in->plane_stride,
+                  in->row_stride, &need) ||
+        in->capacity < need)
+        return ZW_EINVAL;
+    const size_t es = (size_t)ing_elsize(in->dtype);
+    if (!ing_madd(0, in->capacity, es, &bytes) || ((uintptr_t)in->data & (es - 1))) return ZW_EINVAL;
+    HIPOK(hipSetDevice(ctx->device));
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof at);
+    if (hipPointerGetAttributes(&at, in->data) != hipSuccess) {
+        (void)hipGetLastError();  // (an unregistered host pointer)
+        return ZW_EINVAL;
+    }
+    if (at.type != hipMemoryTypeDevice || at.device != ctx->device) return ZW_EINVAL;
+    return ZW_OK;
+}
+
+// Frames from the caller's device tensor.  Everything is checked here, before
+// any encode call queues work.
+extern "C" int zw_pipe_set_input_device(zw_pipe* p, const zw_device_images* in)
+{
+    if (!p) return ZW_EINVAL;
+    if (!in) {
+        p->dev_in = zw_device_images{};
+        return ZW_OK;
+    }
+    if (const int r = check_device_input(p->ctx, in, p->n, (uint32_t)p->w, (uint32_t)p->h)) return r;
+    if (!((p->color == ZW_COLOR_RGB8 && in->channels == 3) || (p->color == ZW_COLOR_RGBA8 && in->channels == 4)))
+        return ZW_EINVAL;
+    if (p->container && in->channels == 4) return ZW_EINVAL;  // (see zw_pipe_set_container)
+    p->dev_in = *in;
     return ZW_OK;
 }
 
@@ -928,9 +982,16 @@ static int chunk_prepass(zw_pipe* p, PipeLane& L, int fa, int na, bool timed, in
     if (uploaded) HIPOK(hipStreamWaitEvent(s, uploaded, 0));
     if (timed) HIPOK(hipEventRecord(L.ev[EV_YUV_BEGIN], s));
     const bool packed = uploaded && p->up_pack;  // (this chunk's frames arrived as RGB)
-    HIPOK(zwk_rgb2yuv(s, p->img_buf(parity) + F * p->img_stride, p->w, p->h, packed ? 3 : p->bpp, p->mbw, p->mbh,
-                      p->d_Y + F * p->ysz, p->d_U + F * p->csz, p->d_V + F * p->csz, p->img_stride, p->ysz, p->csz,
-                      n));
+    if (const zw_device_images& D = p->dev_in; D.data) {  // frames [fa, fa + na) of the caller's tensor
+        const uint8_t* src = (const uint8_t*)D.data + F * D.frame_stride * (size_t)ing_elsize(D.dtype);
+        HIPOK(zwk_rgb2yuv_dev(s, src, D.layout, D.dtype, D.channels, D.frame_stride, D.plane_stride, D.row_stride,
+                              D.scale, D.bias, p->w, p->h, p->mbw, p->mbh, p->d_Y + F * p->ysz, p->d_U + F * p->csz,
+                              p->d_V + F * p->csz, p->ysz, p->csz, n));
+    } else {
+        HIPOK(zwk_rgb2yuv(s, p->img_buf(parity) + F * p->img_stride, p->w, p->h, packed ? 3 : p->bpp, p->mbw, p->mbh,
+                          p->d_Y + F * p->ysz, p->d_U + F * p->csz, p->d_V + F * p->csz, p->img_stride, p->ysz,
+                          p->csz, n));
+    }
     if (read) HIPOK(hipEventRecord(read, s));
     if (timed) HIPOK(hipEventRecord(L.ev[EV_YUV_END], s));
     HIPOK(zwk_analysis(s, p->d_Y + F * p->ysz, p->d_U + F * p->csz, p->d_V + F * p->csz, p->mbw, p->mbh, p->ysz,
@@ -1622,6 +1683,7 @@ extern "C" int zw_pipe_encode_host(zw_pipe* p, int nb, const uint8_t* const* fra
     if (!p || nb < 1 || !frames) return ZW_EINVAL;
     if (p->broken) return ZW_EDEVICE;
     if (p->container) return ZW_EINVAL;  // (the ALPH coder reads the frames set by zw_pipe_set_container)
+    if (p->dev_in.data) return ZW_EINVAL;  // (a device input is set: zw_pipe_set_input_device)
     for (size_t i = 0; i < (size_t)nb * p->n; i++)
         if (!frames[i]) return ZW_EINVAL;
     HIPOK(hipSetDevice(p->ctx->device));
@@ -1864,6 +1926,35 @@ extern "C" int zw_encode_batch_ex(zw_ctx* ctx, int n, const zw_image* imgs, uint
     } else {
         zw_pipe_destroy(p);
     }
+    return r;
+}
+
+// The one-call form over a device tensor (as zw_encode_batch_ex over host
+// images): a pipe of n frames reading `in` (zw_pipe_set_input_device checks it).
+extern "C" int zw_encode_batch_device(zw_ctx* ctx, int n, const zw_device_images* in, uint32_t width, uint32_t height,
+                                      uint8_t quality, uint8_t method, int token_partitions, zw_bytes* outs)
+{
+    if (!ctx || n <= 0 || !in || !outs) return ZW_EINVAL;
+    if (token_partitions != 1 && token_partitions != 2 && token_partitions != 4 && token_partitions != 8)
+        return ZW_EINVAL;
+    for (int i = 0; i < n; i++) {
+        outs[i].data = nullptr;
+        outs[i].len = 0;
+    }
+    if (!encode_dims_ok(width, height)) return ZW_EINVALID_DIMENSIONS;
+    if (quality > 100) return ZW_EINVAL;
+    int r = check_device_input(ctx, in, n, width, height);  // (before the pipe's buffers are allocated)
+    if (r) return r;
+    zw_pipe* p = nullptr;
+    r = zw_pipe_create(ctx, n, width, height, in->channels == 3 ? ZW_COLOR_RGB8 : ZW_COLOR_RGBA8, quality, method, &p);
+    if (r) return r;
+    r = zw_pipe_set_token_partitions(p, token_partitions);
+    if (!r) r = zw_pipe_set_input_device(p, in);
+    if (!r) r = zw_pipe_encode(p);
+    for (int i = 0; i < n && !r; i++) r = zw_pipe_output(p, i, &outs[i]);
+    if (r)
+        for (int i = 0; i < n; i++) zw_bytes_free(&outs[i]);
+    zw_pipe_destroy(p);
     return r;
 }
 

@@ -37,6 +37,7 @@ __all__ = [
     "UpsamplingMethod", "WebPDecoder", "decode_rgb", "decode_rgba", "vp8_decode_rgb", "decode_rgb_batch",
     "decode_rgb_batch_into", "decode_rgba_into", "decode_rgb_into",
     "decode_batch_device", "decode_batch_device_ptr", "decode_webp_batch_device",
+    "encode_batch_device", "encode_batch_device_ptr", "encode_webp_batch_device",
     "yuv_to_rgb", "webp_parse", "encode_frame_lossless", "encode_alpha",
 ]
 
@@ -149,6 +150,9 @@ SIGNATURES = [
                                           ctypes.POINTER(_VP), ctypes.POINTER(_SZ), _U32, _VP, _VP]),
     ("zw_vp8_decode_batch_device", _I, [_VP, _I, ctypes.POINTER(_VP), ctypes.POINTER(_SZ),
                                         ctypes.POINTER(_DeviceImages), ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
+    ("zw_encode_batch_device", _I, [_VP, _I, ctypes.POINTER(_DeviceImages), _U32, _U32, _U8, _U8, _I,
+                                    ctypes.POINTER(_Bytes)]),
+    ("zw_pipe_set_input_device", _I, [_VP, ctypes.POINTER(_DeviceImages)]),
     ("zw_webp_parse", _I, [_VP, _SZ, ctypes.POINTER(_WebpInfo)]),
     ("zw_webp_decode_into", _I, [_VP, _VP, _SZ, _I, _I, _VP, _SZ, _U32, ctypes.POINTER(_U32),
                                  ctypes.POINTER(_U32)]),
@@ -744,6 +748,123 @@ def decode_webp_batch_device(files, out=None, channels=3, layout="chw", dtype="u
     return decode_batch_device(vp8, out, channels, layout, dtype, upsampling, scale, bias, ctx)
 
 
+def _packed_strides(lay, width, height, channels, frame_stride, plane_stride, row_stride):
+    if row_stride is None:
+        row_stride = width * channels if lay == 0 else width
+    if plane_stride is None:
+        plane_stride = row_stride * height
+    if frame_stride is None:
+        frame_stride = row_stride * height if lay == 0 else plane_stride * channels
+    return frame_stride, plane_stride, row_stride
+
+
+def encode_batch_device_ptr(ptr, capacity, n, width, height, channels=3, layout="chw", dtype="u8", quality=75,
+                            method=4, scale=None, bias=None, frame_stride=None, plane_stride=None, row_stride=None,
+                            token_partitions=1, upsampling=0, ctx=None):
+    """zw_encode_batch_device, raw-pointer form: n frames of `width` x `height`
+    read from device memory at `ptr` (`capacity` elements of `dtype`), addressed
+    as decode_batch_device_ptr writes them; strides left None are the packed
+    ones.  u8 elements are the encoder's bytes; an f32 element x gives
+    rint(clamp(float32(x * scale[c]) + bias[c], 0, 255)), ties to even, NaN 0;
+    f16 converts to f32 first.  Channel 3 of 4 is never used.  Returns the list
+    of VP8 frames, the bytes encode_batch gives for those u8 images.  The
+    memory is only read, and every read has completed on return."""
+    c = _ctx(ctx)
+    L = c._lib
+    lay = _layout_code(layout)
+    fs, ps, rs = _packed_strides(lay, width, height, channels, frame_stride, plane_stride, row_stride)
+    d = _DeviceImages(int(ptr), int(capacity), lay, _dtype_code(dtype), int(channels), int(upsampling), int(fs),
+                      int(ps or 0), int(rs), (ctypes.c_float * 4)(*_vec4(scale, 1.0)),
+                      (ctypes.c_float * 4)(*_vec4(bias, 0.0)))
+    if n <= 0:
+        raise ValueError("no frames")
+    outs = (_Bytes * n)()
+    _check(L.zw_encode_batch_device(c.handle, n, ctypes.byref(d), width, height, quality, method, token_partitions,
+                                    outs), "encode_batch_device", EncodingError)
+    return [_take_bytes(L, outs[i]) for i in range(n)]
+
+
+def _tensor_images(tensor, layout, scale, bias, device):
+    """(_DeviceImages, n, width, height, channels) of a 4-d torch tensor
+    [N, C, H, W] or [N, H, W, C] (C = 3 or 4 tells which; `layout` breaks a
+    tie) of uint8 / float16 / float32 on cuda:`device`.  Rows, planes and
+    frames may be padded; any other stride is a ValueError."""
+    import torch
+    tdt = {torch.uint8: 0, torch.float16: 1, torch.float32: 2}
+    if not isinstance(tensor, torch.Tensor) or tensor.dim() != 4:
+        raise ValueError("a 4-d torch tensor [N, C, H, W] or [N, H, W, C]")
+    if not tensor.is_cuda or tensor.device.index != device:
+        raise ValueError(f"the tensor must be on cuda:{device}")
+    if tensor.dtype not in tdt:
+        raise ValueError("the tensor must be uint8, float16 or float32")
+    sh, st = tuple(tensor.shape), tuple(tensor.stride())
+    if min(sh) < 1:
+        raise ValueError("empty tensor")
+    fits_chw, fits_hwc = sh[1] in (3, 4), sh[3] in (3, 4)
+    if fits_chw and fits_hwc:
+        fits_chw = _layout_code(layout) == 1
+    if fits_chw:
+        lay, ch, h, w, fs, ps, rs, unit = 1, sh[1], sh[2], sh[3], st[0], st[1], st[2], (st[3],)
+    elif fits_hwc:
+        lay, ch, h, w, fs, ps, rs, unit = 0, sh[3], sh[1], sh[2], st[0], 0, st[1], (1 if st[2] == sh[3] else 0, st[3])
+    else:
+        raise ValueError("the tensor must be [N, C, H, W] or [N, H, W, C] with C = 3 or 4")
+    if any(u != 1 for u in unit) or min(fs, ps, rs) < 0:
+        raise ValueError("only rows, planes and frames may be padded (innermost stride 1)")
+    capacity = tensor.untyped_storage().nbytes() // tensor.element_size() - tensor.storage_offset()
+    d = _DeviceImages(tensor.data_ptr(), capacity, lay, tdt[tensor.dtype], ch, 0, fs, ps, rs,
+                      (ctypes.c_float * 4)(*_vec4(scale, 1.0)), (ctypes.c_float * 4)(*_vec4(bias, 0.0)))
+    return d, sh[0], w, h, ch
+
+
+def encode_batch_device(tensor, quality=75, method=4, layout="chw", scale=None, bias=None, token_partitions=1,
+                        ctx=None):
+    """Encode the frames of a torch tensor on the context's device with no
+    download, upload or host copy (zw_encode_batch_device); returns the list of
+    VP8 frames.
+
+    tensor: 4-d [N, C, H, W] or [N, H, W, C] with C = 3 or 4 (a tensor both
+    shapes fit is read as `layout`), uint8, float16 or float32.  Its innermost
+    stride must be 1 (and the channel stride 1 for HWC): rows, planes and
+    frames may be padded, nothing else; ValueError otherwise, or for a tensor of
+    another device.  The pixel rule is encode_batch_device_ptr's (scale / bias:
+    None, one number, or per-channel values); the streams are encode_batch's of
+    the u8 images it makes.  `capacity` is what the tensor's storage holds from
+    its first element.  torch's current stream is synchronised before the call;
+    the tensor is only read, and every read has completed on return.
+
+    torch must initialise its HIP runtime before libzwebp.so loads in the
+    process (see decode_batch_device)."""
+    import torch
+    c = _ctx(ctx)
+    d, n, w, h, _ = _tensor_images(tensor, layout, scale, bias, c.device)
+    torch.cuda.current_stream(torch.device("cuda", c.device)).synchronize()
+    L = c._lib
+    outs = (_Bytes * n)()
+    _check(L.zw_encode_batch_device(c.handle, n, ctypes.byref(d), w, h, quality, method, token_partitions, outs),
+           "encode_batch_device", EncodingError)
+    return [_take_bytes(L, outs[i]) for i in range(n)]
+
+
+def encode_webp_batch_device(tensor, quality=75, method=4, layout="chw", scale=None, bias=None, ctx=None):
+    """encode_batch_device with container output: a RIFF "VP8 " file per frame,
+    the bytes of encode_webp_batch over the RGB8 images the pixel rule makes.
+    3 channels only (ValueError for 4: the ALPH chunk is coded on the host from
+    host frames)."""
+    c = _ctx(ctx)
+    d, n, w, h, ch = _tensor_images(tensor, layout, scale, bias, c.device)
+    if ch != 3:
+        raise ValueError("container output from a device tensor takes 3 channels")
+    p = Pipeline(n, w, h, ColorType.Rgb8, quality, method, ctx=c)
+    try:
+        p.set_container()
+        p.set_input(tensor, layout, scale, bias)
+        p.encode()
+        return [p.output(i) for i in range(n)]
+    finally:
+        p.close()
+
+
 def webp_frame_width(vp8):
     """Width field of a VP8 key-frame header (frame tag + start code + 14-bit width);
     0 for a frame too short to hold one (the decode then reports the error)."""
@@ -1040,6 +1161,27 @@ class Pipeline:
             ptrs = (ctypes.c_void_p * len(self._host_frames))(*[f.ctypes.data for f in self._host_frames])
         _check(self._lib.zw_pipe_set_container(self._h, 1 if enable else 0, ptrs), "zw_pipe_set_container",
                EncodingError)
+
+    def set_input(self, tensor, layout="chw", scale=None, bias=None):
+        """Read the n frames from a torch tensor on the pipeline's device
+        (zw_pipe_set_input_device; the tensor and pixel rule of
+        encode_batch_device) in encode / encode_repeat / run_pass1 /
+        run_device, instead of the packed buffer; set_input(None) switches
+        back.  The pipeline must be Rgb8 for 3 channels, Rgba8 for 4.  It keeps
+        the tensor referenced; torch's current stream is synchronised here, and
+        work queued on the tensor later is the caller's to order."""
+        if tensor is None:
+            _check(self._lib.zw_pipe_set_input_device(self._h, None), "zw_pipe_set_input_device", EncodingError)
+            self._input = None
+            return
+        import torch
+        d, n, w, h, _ = _tensor_images(tensor, layout, scale, bias, self.ctx.device)
+        if (n, w, h) != (self.n, self.width, self.height):
+            raise ValueError(f"the tensor must hold {self.n} frames of {self.width}x{self.height}")
+        torch.cuda.current_stream(torch.device("cuda", self.ctx.device)).synchronize()
+        _check(self._lib.zw_pipe_set_input_device(self._h, ctypes.byref(d)), "zw_pipe_set_input_device",
+               EncodingError)
+        self._input = tensor
 
     def set_token_partitions(self, n):
         """Token partitions (1, 2, 4, 8) of every frame (zw_pipe_set_token_partitions)."""

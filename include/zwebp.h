@@ -253,6 +253,34 @@ typedef struct {
 } zw_device_images;
 int zw_vp8_decode_batch_device(zw_ctx *ctx, int n, const uint8_t *const *data, const size_t *lens,
                                const zw_device_images *out, uint32_t *width, uint32_t *height);
+/* Device-resident encode (new): n frames of one size read straight from the
+ * caller's device memory, a batch tensor described as above (`upsampling` must
+ * be 0; the same addressing, stride bounds and non-overlap rule).  Nothing
+ * crosses from the host: the conversion kernel (k_rgb2yuv_dev) reads the tensor
+ * and writes the encoder's Y/U/V planes; no packed u8 image is made in between.
+ *
+ * Pixel rule: input element x of channel c gives the byte v the encoder sees.
+ *   ZW_DTYPE_U8   v = x (scale and bias are ignored);
+ *   ZW_DTYPE_F32  t = x * scale[c], a rounded multiply; t = t + bias[c], a
+ *                 rounded add (never fused); v = 0 if t is NaN, else
+ *                 (uint8) rint(min(max(t, 0), 255)), round-half-to-even
+ *                 (+-inf therefore clamps);
+ *   ZW_DTYPE_F16  x converted to f32 (exact), then the f32 rule.
+ * Frame i's bitstream is byte for byte what zw_encode_batch_ex returns for the
+ * packed RGB8 / RGBA8 image this rule makes.  With 4 channels, channel 3 is
+ * never used (the VP8 payload does not read alpha).
+ *
+ * Checked before anything is queued, each failure ZW_EINVAL: NULL arguments; a
+ * bad layout, dtype, channels (3 | 4) or upsampling; strides below the bounds;
+ * overlapping frames; capacity below the last addressed element + 1; `data`
+ * that hipPointerGetAttributes does not report as device memory on the
+ * context's device (or that is not aligned to its element).  Dimensions are
+ * checked as zw_pipe_create checks them.  The tensor is only read (elements
+ * in the gaps never), and the call returns after every read has completed;
+ * the caller makes sure no earlier work of its own still writes `data`.
+ * token_partitions as zw_encode_frame_lossy_ex. */
+int zw_encode_batch_device(zw_ctx *ctx, int n, const zw_device_images *in, uint32_t width, uint32_t height,
+                           uint8_t quality, uint8_t method, int token_partitions, zw_bytes *outs);
 /* WebPDecoder::new (container parse, no decoding; lossy subset: ALPH, VP8L and
  * animation return ZW_EUNSUPPORTED with info filled as far as parsed). */
 int zw_webp_parse(const uint8_t *data, size_t len, zw_webp_info *info);
@@ -405,6 +433,16 @@ int zw_pipe_upload(zw_pipe *p, int frame, const uint8_t *data, size_t len);
  * valid while the pipe encodes); host_frames may be NULL for L8 / RGB8.
  * enable = 0 switches back to bare frames. */
 int zw_pipe_set_container(zw_pipe *p, int enable, const uint8_t *const *host_frames);
+/* Device-tensor input (see zw_encode_batch_device for the pixel rule and the
+ * checks, all made here): later zw_pipe_encode, zw_pipe_encode_repeat,
+ * zw_pipe_run_pass1 and zw_pipe_run_device read the pipe's n frames from `in`
+ * (copied; `in->data` must stay valid and unwritten while they run), not from
+ * the packed buffer.  NULL switches back.  The pipe must be RGB8 with channels
+ * 3 or RGBA8 with channels 4.  Each encode call returns after every read has
+ * completed.  While a device input is set zw_pipe_encode_host returns
+ * ZW_EINVAL, and so does container output of an RGBA8 pipe, in either order
+ * of the two calls (the ALPH chunk is coded on the host from host frames). */
+int zw_pipe_set_input_device(zw_pipe *p, const zw_device_images *in);
 /* Token partitions (1, 2, 4, 8) of every frame the pipe emits (default 1);
  * see zw_encode_frame_lossy_ex.  ZW_EINVAL for any other count. */
 int zw_pipe_set_token_partitions(zw_pipe *p, int nparts);
