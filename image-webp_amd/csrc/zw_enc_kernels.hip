@@ -1,12 +1,11 @@
-// zw_enc_kernels.hip -- device half of the lossy encoder (gfx950).
+// zw_enc_kernels.hip -- the encode pass of the lossy encoder (gfx950).
 //
-//   k_rgb2yuv     convert_image_yuv / convert_image_y      (decoder/yuv.rs:656, :806)
-//   k_analysis4   analyze_image per-MB alpha + histogram    (encoder/analysis.rs:964)
-//   k_segments    k-means, segment quant, matrices, lambdas (analysis.rs:1029, :1145;
-//                 vp8.rs:2278-2388, types.rs:806)
-//   k_encode      one encode pass over a batch of frames:   (vp8.rs:1281-1488)
+//   k_encode_*    one encode pass over a batch of frames:   (vp8.rs:1281-1488)
 //                 RD mode search (pick_best_intra16/intra4/uv), final transform,
 //                 quantization (simple or trellis), recon, error diffusion, skip.
+//
+// (The conversion, analysis and segment kernels that run before it are in
+// zw_prepass_kernels.hip, the block quantiser kernels in zw_quant_kernels.hip.)
 //
 // Parallel structure: one workgroup per frame, NW waves.  Macroblock rows are
 // dealt to waves round-robin and advance as an x+2y wavefront (a row may work
@@ -68,581 +67,11 @@
 #ifndef ZW_LUMA_PRIO
 #define ZW_LUMA_PRIO 0
 #endif
-// Pass 1's chroma chain: one wave (pair form) or two (quad form, one wave per
-// plane).  The row-parallel kernels take the two-wave chain: it bounds their
-// pass 1 (one 1080p frame: 27.7 -> 22.1 ms), and their pass-1 workgroups then
-// run two waves (the chain's two planes; two luma rows elsewhere).  The batch
-// kernels keep one chain wave: there a second one costs a luma wave and
-// measured slower (34.4 -> 35.0 ms per 256 1080p frames).
-#ifndef ZW_UVQ_CHAIN_ROWS
-#define ZW_UVQ_CHAIN_ROWS 1
-#endif
-#ifndef ZW_UVQ_CHAIN_BATCH
-#define ZW_UVQ_CHAIN_BATCH 0
-#endif
-// The per-MB stage loops of the frame-pair kernel: ZW_PAIR_UNROLL 1 emits
-// each stage twice (constant frame index), 0 once (a two-trip loop); measured
-// per 256 1080p frames: pass 2 29.80 vs 30.26 ms, pass 1 the same.
-#ifndef ZW_PAIR_UNROLL
-#define ZW_PAIR_UNROLL 1
-#endif
-// Pass 1 loads the MB's source words and alpha at the top of its iteration,
-// in flight during the wait for the row above; pass 2 fetches them one MB
-// ahead.  (Fetched ahead, the words do not stay in registers: each is spilled
-// to scratch right after its load, so the three loads run one after another,
-// each also waiting for the previous MB's stores -- vmcnt counts stores.
-// Measured per 256 1080p frames: pass 1 29.12 -> 28.98 ms loading at the top,
-// pass 2 37.38 -> 37.64 ms.)  An expression of the kernel's PASS.
-#ifndef ZW_FETCH_AHEAD
-#define ZW_FETCH_AHEAD (PASS == 2)
-#endif
-// k_analysis4: 4-MB groups per wave (measured, analysis + segments per 256
-// 1080p frames: 1 1.375, 2 1.47, 4 1.41 ms).
-#ifndef ZW_AN4_GPW
-#define ZW_AN4_GPW 1
-#endif
 
 template <int PASS> struct PassShape {
     static constexpr int NW = PASS == 1 ? ZW_NW1 : ZW_NW2;
     static constexpr int WG = NW * 64;
 };
-
-// ---------------------------------------------------------------------------
-// RGB(A)/L(A) -> padded YUV420.  One thread per chroma sample; it produces the
-// 2x2 luma pixels and the U/V sample.  Padding (x >= w, y >= h) is produced by
-// clamping the source coordinate, which equals the reference's edge
-// replication (yuv.rs:765-803).
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ int rgb_y(const uint8_t* p)
-{
-    return (16839 * p[0] + 33059 * p[1] + 6420 * p[2] + (1 << 15) + (16 << 16)) >> 16;
-}
-__device__ __forceinline__ int rgb_u(const uint8_t* p) { return -9719 * p[0] - 19081 * p[1] + 28800 * p[2] + (128 << 16); }
-__device__ __forceinline__ int rgb_v(const uint8_t* p) { return 28800 * p[0] - 24116 * p[1] - 4684 * p[2] + (128 << 16); }
-
-// chroma sample (cx, cy) of one frame and its 2x2 luma pixels
-__device__ __forceinline__ void rgb2yuv_sample(const uint8_t* __restrict__ im, int w, int h, int bpp, int mbw, int cx,
-                                               int cy, uint8_t* __restrict__ Yf, uint8_t* __restrict__ Uf,
-                                               uint8_t* __restrict__ Vf)
-{
-    const int cw = mbw * 8, lw = mbw * 16;
-    const int acw = (w + 1) / 2, ach = (h + 1) / 2;
-    const int scx = cx < acw ? cx : acw - 1, scy = cy < ach ? cy : ach - 1;
-    int xs[2] = {min(2 * scx, w - 1), min(2 * scx + 1, w - 1)};
-    int ys[2] = {min(2 * scy, h - 1), min(2 * scy + 1, h - 1)};
-    // luma: the 2x2 pixels this thread owns in the padded plane
-#pragma unroll
-    for (int dy = 0; dy < 2; dy++)
-#pragma unroll
-        for (int dx = 0; dx < 2; dx++) {
-            int px = min(2 * cx + dx, w - 1), py = min(2 * cy + dy, h - 1);
-            const uint8_t* p = im + ((size_t)py * w + px) * bpp;
-            Yf[(size_t)(2 * cy + dy) * lw + 2 * cx + dx] = (uint8_t)(bpp <= 2 ? p[0] : rgb_y(p));
-        }
-    uint8_t uo = 127, vo = 127;
-    if (bpp > 2) {
-        int su = 0, sv = 0;
-#pragma unroll
-        for (int dy = 0; dy < 2; dy++)
-#pragma unroll
-            for (int dx = 0; dx < 2; dx++) {
-                const uint8_t* p = im + ((size_t)ys[dy] * w + xs[dx]) * bpp;
-                su += rgb_u(p);
-                sv += rgb_v(p);
-            }
-        uo = (uint8_t)((su + (1 << 17)) >> 18);
-        vo = (uint8_t)((sv + (1 << 17)) >> 18);
-    }
-    Uf[(size_t)cy * cw + cx] = uo;
-    Vf[(size_t)cy * cw + cx] = vo;
-}
-
-extern "C" __global__ void k_rgb2yuv(const uint8_t* __restrict__ img, int w, int h, int bpp, int mbw, int mbh,
-                                     uint8_t* __restrict__ Y, uint8_t* __restrict__ U, uint8_t* __restrict__ V,
-                                     size_t img_stride, size_t ysz, size_t csz)
-{
-    const int cw = mbw * 8, chh = mbh * 8;
-    const int f = blockIdx.y;
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= cw * chh) return;
-    rgb2yuv_sample(img + (size_t)f * img_stride, w, h, bpp, mbw, idx % cw, idx / cw, Y + (size_t)f * ysz,
-                   U + (size_t)f * csz, V + (size_t)f * csz);
-}
-
-// Row-coalesced form for 3- and 4-byte pixels: one thread per 8x2 luma pixels
-// (4 chroma samples), so a wave reads 64 consecutive 8-pixel runs of two rows
-// with 16-byte (RGBA) or 8-byte (RGB) loads and writes 8-byte luma and 4-byte
-// chroma words.  Runs that reach the right edge and the padding rows below the
-// image take the per-sample path (edge replication).  The host launches it
-// only when every run is aligned for those loads.
-template <int BPP>
-__device__ __forceinline__ void rgb_run8(const uint8_t* __restrict__ row, uint32_t px[8])  // 0x..BBGGRR
-{
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-    if (BPP == 4) {
-        const u32x4 a = __builtin_nontemporal_load((const u32x4*)row);
-        const u32x4 b = __builtin_nontemporal_load((const u32x4*)(row + 16));
-        px[0] = a.x; px[1] = a.y; px[2] = a.z; px[3] = a.w;
-        px[4] = b.x; px[5] = b.y; px[6] = b.z; px[7] = b.w;
-    } else {
-        const u32x2 a = __builtin_nontemporal_load((const u32x2*)row);
-        const u32x2 b = __builtin_nontemporal_load((const u32x2*)(row + 8));
-        const u32x2 c = __builtin_nontemporal_load((const u32x2*)(row + 16));
-        const uint32_t wd[6] = {a.x, a.y, b.x, b.y, c.x, c.y};
-#pragma unroll
-        for (int q = 0; q < 2; q++) {  // 4 pixels in 3 words
-            const uint32_t w0 = wd[3 * q], w1 = wd[3 * q + 1], w2 = wd[3 * q + 2];
-            px[4 * q] = w0;
-            px[4 * q + 1] = __builtin_amdgcn_alignbyte(w1, w0, 3);
-            px[4 * q + 2] = __builtin_amdgcn_alignbyte(w2, w1, 2);
-            px[4 * q + 3] = w2 >> 8;
-        }
-    }
-}
-
-template <int BPP>
-__global__ __launch_bounds__(256) void k_rgb2yuv_rows(const uint8_t* __restrict__ img, int w, int h, int mbw, int mbh,
-                                                      uint8_t* __restrict__ Y, uint8_t* __restrict__ U,
-                                                      uint8_t* __restrict__ V, size_t img_stride, size_t ysz,
-                                                      size_t csz)
-{
-    const int cw = mbw * 8, chh = mbh * 8, lw = mbw * 16, gpr = mbw * 2;  // 4-sample groups per chroma row
-    const int f = blockIdx.y;
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= gpr * chh) return;
-    const int g = idx % gpr, cy = idx / gpr;
-    const int cx0 = 4 * g, px0 = 8 * g;
-    const uint8_t* im = img + (size_t)f * img_stride;
-    uint8_t* Yf = Y + (size_t)f * ysz;
-    uint8_t* Uf = U + (size_t)f * csz;
-    uint8_t* Vf = V + (size_t)f * csz;
-    if (px0 + 8 <= w && cy < (h + 1) / 2) {
-        const int r0 = 2 * cy, r1 = min(2 * cy + 1, h - 1);
-        uint32_t a[8], b[8];
-        rgb_run8<BPP>(im + ((size_t)r0 * w + px0) * BPP, a);
-        rgb_run8<BPP>(im + ((size_t)r1 * w + px0) * BPP, b);
-        const uint32_t ya[2] = {pk_y4(a[0], a[1], a[2], a[3]), pk_y4(a[4], a[5], a[6], a[7])};
-        const uint32_t yb[2] = {pk_y4(b[0], b[1], b[2], b[3]), pk_y4(b[4], b[5], b[6], b[7])};
-        uint32_t uw = 0, vw = 0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int su = pk_u(a[2 * j]) + pk_u(a[2 * j + 1]) + pk_u(b[2 * j]) + pk_u(b[2 * j + 1]) + (512 << 16);
-            const int sv = pk_v(a[2 * j]) + pk_v(a[2 * j + 1]) + pk_v(b[2 * j]) + pk_v(b[2 * j + 1]) + (512 << 16);
-            uw |= (uint32_t)((su + (1 << 17)) >> 18) << (8 * j);
-            vw |= (uint32_t)((sv + (1 << 17)) >> 18) << (8 * j);
-        }
-        *(uint2*)(Yf + (size_t)(2 * cy) * lw + px0) = make_uint2(ya[0], ya[1]);
-        *(uint2*)(Yf + (size_t)(2 * cy + 1) * lw + px0) = make_uint2(yb[0], yb[1]);
-        *(uint32_t*)(Uf + (size_t)cy * cw + cx0) = uw;
-        *(uint32_t*)(Vf + (size_t)cy * cw + cx0) = vw;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; j++) rgb2yuv_sample(im, w, h, BPP, mbw, cx0 + j, cy, Yf, Uf, Vf);
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Analysis (analysis.rs:964), four MBs a wave: 16 lanes an MB, lane j working
-// three of the MB's 48 (block, mode) items -- luma block j under DC and under
-// TM, chroma block j & 7 (U 0-3, V 4-7) under mode j >> 3 -- so every lane has
-// work and the four MBs' chains overlap.  Predictors use source pixels; on the
-// MB-padded planes libwebp's import/replicate rules reduce to direct reads
-// (analysis.rs:520-745).
-// ---------------------------------------------------------------------------
-// An MB and its edge pixels staged in LDS.
-struct AnalysisTile {
-    uint32_t y[16][4];     // luma rows, 4 packed pixels per word
-    uint32_t c[2][8][2];   // U, V rows
-    uint32_t ytop[4], ctop[2][2];
-    uint8_t yleft[16], cleft[2][8];
-    uint8_t corner[4];     // Y, U, V
-};
-
-// One item: its 16 coefficient bins (min(|c| >> 3, 31)), the count of bin 0 and the largest bin.
-DI void an_item(const AnalysisTile* A, bool luma, int mode, int b, bool ht, bool hl, int bins[16], int& z, int& vmax)
-{
-    const int pl = b >> 2;  // chroma plane
-    const int bb = luma ? b : (b & 3);
-    const int bx = luma ? (bb & 3) : (bb & 1), by = luma ? (bb >> 2) : (bb >> 1);
-    uint32_t st = 0, sl = 0;
-    if (luma) {
-#pragma unroll
-        for (int w = 0; w < 4; w++) {
-            st = __builtin_amdgcn_sad_u8(A->ytop[w], 0u, st);
-            sl = __builtin_amdgcn_sad_u8(((const uint32_t*)A->yleft)[w], 0u, sl);
-        }
-    } else {
-#pragma unroll
-        for (int w = 0; w < 2; w++) {
-            st = __builtin_amdgcn_sad_u8(A->ctop[pl][w], 0u, st);
-            sl = __builtin_amdgcn_sad_u8(((const uint32_t*)A->cleft[pl])[w], 0u, sl);
-        }
-    }
-    const uint32_t s2 = ht && hl ? st + sl : (ht ? 2 * st : 2 * sl);
-    const int dcv = (ht || hl) ? (luma ? (int)((s2 + 16) >> 5) : (int)((s2 + 8) >> 4)) : 0x80;
-    const int corner = A->corner[luma ? 0 : 1 + pl];
-    int d[16];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const int r = by * 4 + i;
-        const uint32_t srow = luma ? A->y[r][bx] : A->c[pl][r][bx];
-        const int L = luma ? A->yleft[r] : A->cleft[pl][r];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int cidx = bx * 4 + j;
-            const uint32_t tw = luma ? A->ytop[cidx >> 2] : A->ctop[pl][cidx >> 2];
-            const int T = (int)((tw >> (8 * (cidx & 3))) & 255u);
-            const int tm = (ht && hl) ? clamp255(L + T - corner) : (hl ? L : (ht ? T : 129));
-            const int p = mode == 0 ? dcv : tm;
-            d[i * 4 + j] = (int)((srow >> (8 * j)) & 255u) - p;
-        }
-    }
-    int o[16];
-    fdct16_pk(d, o);
-    z = 0;
-    vmax = 0;
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        bins[k] = min(iabs(o[k]) >> 3, 31);
-        z += bins[k] == 0;
-        vmax = max(vmax, bins[k]);
-    }
-}
-DI int max8(int v)  // max within aligned 8-lane groups
-{
-    v = max(v, DPP(v, 0xB1));
-    v = max(v, DPP(v, 0x4E));
-    return max(v, DPP(v, 0x141));
-}
-DI int an_red8(int v)  // sum within aligned 8-lane groups
-{
-    v += DPP(v, 0xB1);
-    v += DPP(v, 0x4E);
-    return v + DPP(v, 0x141);
-}
-DI int max16(int v)
-{
-    v = max8(v);
-    return max(v, DPP(v, 0x140));
-}
-typedef unsigned an_v4u __attribute__((ext_vector_type(4)));
-typedef unsigned an_v2u __attribute__((ext_vector_type(2)));
-extern "C" __global__ __launch_bounds__(256) void k_analysis4(const uint8_t* __restrict__ Y, const uint8_t* __restrict__ U,
-                                                              const uint8_t* __restrict__ V, int mbw, int mbh,
-                                                              size_t ysz, size_t csz, uint8_t* __restrict__ alpha,
-                                                              uint32_t* __restrict__ histo)
-{
-    __shared__ AnalysisTile tile[4][4];   // [wave][MB]
-    __shared__ uint32_t hist[4][4][4][32];  // [wave][MB][histogram][bin] (only when some bin 0 is short)
-    __shared__ uint32_t ahist[256];
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, mi = lane >> 4, j = lane & 15;
-    const int f = blockIdx.y;
-    const int nmb = mbw * mbh;
-    ahist[threadIdx.x] = 0;
-    __syncthreads();
-    const int ys = mbw * 16, cs = mbw * 8;
-    const uint8_t* Yf = Y + (size_t)f * ysz;
-    const uint8_t* Uf = U + (size_t)f * csz;
-    const uint8_t* Vf = V + (size_t)f * csz;
-    AnalysisTile* A = &tile[wv][mi];
-#pragma unroll 1
-    for (int it = 0; it < ZW_AN4_GPW; it++) {
-        const int mb = ((blockIdx.x * ZW_AN4_GPW + it) * 4 + wv) * 4 + mi;
-        const bool in = mb < nmb;
-        const int mbx = in ? mb % mbw : 0, mby = in ? mb / mbw : 0;
-        const bool ht = mby > 0, hl = mbx > 0;
-        // ---- stage the MB and its edges (lane j: luma row j, chroma row j & 7 of plane j >> 3)
-        {
-            const int pl = j >> 3, cr = j & 7;
-            const uint8_t* Cf = pl ? Vf : Uf;
-            an_v4u yr = {0u, 0u, 0u, 0u};
-            an_v2u cw = {0u, 0u};
-            uint32_t yl = 0, cl = 0;
-            if (in) {
-                const uint8_t* yp = Yf + (size_t)(mby * 16 + j) * ys + mbx * 16;
-                const uint8_t* cp = Cf + (size_t)(mby * 8 + cr) * cs + mbx * 8;
-                yr = *(const an_v4u*)yp;
-                cw = *(const an_v2u*)cp;
-                if (hl) {
-                    yl = yp[-1];
-                    cl = cp[-1];
-                }
-            }
-            wsync();  // (the previous group's reads of the tile are done)
-            *(an_v4u*)A->y[j] = yr;
-            *(an_v2u*)A->c[pl][cr] = cw;
-            A->yleft[j] = (uint8_t)yl;
-            A->cleft[pl][cr] = (uint8_t)cl;
-            if (j < 6) {
-                uint32_t t0 = 0, t1 = 0, t2 = 0, t3 = 0;
-                if (in && ht) {
-                    if (j == 0) {
-                        const an_v4u t = *(const an_v4u*)(Yf + (size_t)(mby * 16 - 1) * ys + mbx * 16);
-                        t0 = t.x; t1 = t.y; t2 = t.z; t3 = t.w;
-                    } else if (j < 3) {
-                        const an_v2u t = *(const an_v2u*)((j == 1 ? Uf : Vf) + (size_t)(mby * 8 - 1) * cs + mbx * 8);
-                        t0 = t.x; t1 = t.y;
-                    } else if (hl) {
-                        const uint8_t* cp = j == 3 ? Yf + (size_t)(mby * 16 - 1) * ys + mbx * 16 - 1
-                                                   : (j == 4 ? Uf : Vf) + (size_t)(mby * 8 - 1) * cs + mbx * 8 - 1;
-                        t0 = *cp;
-                    }
-                }
-                if (j == 0) {
-                    A->ytop[0] = t0; A->ytop[1] = t1; A->ytop[2] = t2; A->ytop[3] = t3;
-                } else if (j < 3) {
-                    A->ctop[j - 1][0] = t0;
-                    A->ctop[j - 1][1] = t1;
-                } else {
-                    A->corner[j - 3] = (uint8_t)t0;
-                }
-            }
-            wsync();
-        }
-        // ---- the three items: luma block j under DC (A) and TM (B), chroma block j & 7 under mode j >> 3 (C)
-        int bins[16], zA, vA, zB, vB, zC, vC;
-        an_item(A, true, 0, j, ht, hl, bins, zA, vA);
-        an_item(A, true, 1, j, ht, hl, bins, zB, vB);
-        an_item(A, false, j >> 3, j & 7, ht, hl, bins, zC, vC);
-        // per histogram (luma DC, luma TM, chroma DC in lanes j < 8, chroma TM in j >= 8):
-        // the bin-0 count and the largest bin
-        const int z0 = red16(zA), z1 = red16(zB), z23 = an_red8(zC);
-        const int v0 = max16(vA), v1 = max16(vB), v23 = max8(vC);
-        // fast path: bin 0 holding at least half of a histogram's
-        // coefficients is its largest count, and the last non-empty bin is the largest bin
-        const bool ok = 2 * z0 >= 256 && 2 * z1 >= 256 && 2 * z23 >= 128;
-        int a0, a1, a23;
-        if (__ballot(in && !ok) == 0ull) {
-            a0 = z0 > 1 ? (int)(510u * (uint32_t)v0 / (uint32_t)z0) : 0;
-            a1 = z1 > 1 ? (int)(510u * (uint32_t)v1 / (uint32_t)z1) : 0;
-            a23 = z23 > 1 ? (int)(510u * (uint32_t)v23 / (uint32_t)z23) : 0;
-        } else {
-            // exact histograms: bin 0 counted in the lane, the other bins by LDS atomics
-            uint32_t* H = &hist[wv][mi][0][0];
-#pragma unroll
-            for (int k = 0; k < 8; k++) (&hist[wv][0][0][0])[64 * k + lane] = 0;
-            wsync();
-#pragma unroll 1
-            for (int t = 0; t < 3; t++) {
-                int zz, vv;
-                const int h = t < 2 ? t : 2 + (j >> 3);
-                an_item(A, t < 2, t < 2 ? t : j >> 3, t < 2 ? j : j & 7, ht, hl, bins, zz, vv);
-#pragma unroll
-                for (int k = 0; k < 16; k++)
-                    if (bins[k]) atomicAdd(&H[h * 32 + bins[k]], 1u);
-                if (zz) atomicAdd(&H[h * 32], (uint32_t)zz);
-            }
-            wsync();
-            int av[4];
-#pragma unroll
-            for (int h = 0; h < 4; h++) {
-                const uint32_t c0 = H[h * 32 + 2 * j], c1 = H[h * 32 + 2 * j + 1];
-                const int mx = max16((int)max(c0, c1));
-                const int lnz = max16(c1 ? 2 * j + 1 : (c0 ? 2 * j : -1));
-                av[h] = mx > 1 ? (int)(510u * (uint32_t)max(lnz, 0) / (uint32_t)mx) : 0;
-            }
-            a0 = av[0];
-            a1 = av[1];
-            a23 = j < 8 ? av[2] : av[3];
-        }
-        const int a3 = __shfl(a23, (lane & ~15) | 8);  // chroma TM's, from lane 8 of the MB
-        if (j == 0 && in) {
-            const int best = max(-1, max(a0, a1));
-            const int buv = max(-1, max(a23, a3));
-            int al = (3 * best + buv + 2) >> 2;
-            al = 255 - al;
-            al = al < 0 ? 0 : (al > 255 ? 255 : al);
-            alpha[(size_t)f * nmb + mb] = (uint8_t)al;
-            atomicAdd(&ahist[al], 1u);
-        }
-    }
-    __syncthreads();
-    const uint32_t c = ahist[threadIdx.x];
-    if (c) atomicAdd(&histo[(size_t)f * 256 + threadIdx.x], c);
-}
-
-// ---------------------------------------------------------------------------
-// Segments: one thread per frame.  k-means over the alpha histogram
-// (assign_segments_kmeans analysis.rs:1029), per-segment quant via the
-// reference's f64 fast_math pow (compute_segment_quant :1145; this file is
-// built with -ffp-contract=off), matrices/lambdas (Segment::init_matrices
-// types.rs:806), segment tree probabilities (vp8.rs:2340-2368).
-// ---------------------------------------------------------------------------
-__device__ double fm_log2(double x)
-{
-    unsigned long long bits = __double_as_longlong(x);
-    long long e = (long long)((bits >> 52) & 0x7FF) - 1023;
-    unsigned long long mb = (bits & 0x000FFFFFFFFFFFFFull) | 0x3FF0000000000000ull;
-    double m = __longlong_as_double((long long)mb);
-    double y = (m - 1.0) / (m + 1.0);
-    double y2 = y * y;
-    const double C0 = 2.8853900817779268, C1 = 0.9617966939259756, C2 = 0.5770780163555854,
-                 C3 = 0.4121985831111324, C4 = 0.3205988987531030;
-    double poly = C0 + y2 * (C1 + y2 * (C2 + y2 * (C3 + y2 * C4)));
-    return (double)e + y * poly;
-}
-__device__ double fm_exp2(double x)
-{
-    if (x < -1022.0) x = -1022.0;
-    if (x > 1023.0) x = 1023.0;
-    long long xi = x >= 0.0 ? (long long)x : (long long)x - 1;
-    double xf = x - (double)xi;
-    const double LN2 = 0.6931471805599453;
-    const double C1 = LN2, C2 = LN2 * LN2 / 2.0, C3 = LN2 * LN2 * LN2 / 6.0, C4 = LN2 * LN2 * LN2 * LN2 / 24.0,
-                 C5 = LN2 * LN2 * LN2 * LN2 * LN2 / 120.0;
-    double poly = 1.0 + xf * (C1 + xf * (C2 + xf * (C3 + xf * (C4 + xf * C5))));
-    double scale = __longlong_as_double((long long)((unsigned long long)(xi + 1023) << 52));
-    return poly * scale;
-}
-__device__ double fm_pow(double x, double n)
-{
-    if (x <= 0.0) return 0.0;
-    if (x == 1.0 || n == 0.0) return 1.0;
-    if (n == 1.0) return x;
-    return fm_exp2(n * fm_log2(x));
-}
-__device__ int segment_quant(int base, int alpha, int sns)
-{
-    double amp = 0.9 * (double)sns / 100.0 / 128.0;
-    double expn = 1.0 - amp * (double)alpha;
-    if (expn <= 0.0) return base;
-    double cb = 1.0 - ((double)base / 127.0);
-    double c = fm_pow(cb, expn);
-    int q = (int)(127.0 * (1.0 - c));
-    return q < 0 ? 0 : (q > 127 ? 127 : q);
-}
-
-__device__ void matrix_init(ZwMatrix& m, int qdc, int qac, int bdc, int bac)
-{
-    m.q[0] = (uint32_t)qdc;
-    m.q[1] = (uint32_t)qac;
-    for (int i = 0; i < 2; i++) {
-        uint32_t b = i ? bac : bdc;
-        m.iq[i] = (1u << 17) / m.q[i];
-        m.bias[i] = ((b << 17) + 128) >> 8;
-        m.zthresh[i] = ((1u << 17) - 1 - m.bias[i]) / m.iq[i];
-    }
-}
-
-__device__ void segment_init(ZwSegment& s, int qi, int delta)
-{
-    int ydc = d_DC_QUANT[qi], yac = d_AC_QUANT[qi];
-    int y2dc = d_DC_QUANT[qi] * 2;
-    int y2ac = (int)d_AC_QUANT[qi] * 155 / 100;
-    if (y2ac < 8) y2ac = 8;
-    int uvdc = d_DC_QUANT[qi], uvac = d_AC_QUANT[qi];
-    matrix_init(s.y1, ydc, yac, 96, 110);
-    matrix_init(s.y2, y2dc, y2ac, 96, 108);
-    matrix_init(s.uv, uvdc, uvac, 110, 115);
-    for (int i = 0; i < 16; i++) {
-        uint32_t q = i == 0 ? (uint32_t)ydc : (uint32_t)yac;
-        s.sharpen[i] = (uint16_t)(((uint32_t)d_VP8_FREQ_SHARPENING[i] * q) >> 11);
-    }
-    uint32_t qi4 = ((uint32_t)ydc + 15u * (uint32_t)yac + 8) >> 4;
-    uint32_t qi16 = ((uint32_t)y2dc + 15u * (uint32_t)y2ac + 8) >> 4;
-    uint32_t quv = ((uint32_t)uvdc + 15u * (uint32_t)uvac + 8) >> 4;
-#define MAX1(v) ((v) ? (v) : 1u)
-    s.lt_i4 = MAX1((7 * qi4 * qi4) >> 3);
-    s.lt_i16 = MAX1((qi16 * qi16) >> 2);
-    s.lt_uv = MAX1((quv * quv) << 1);
-    s.l_i4 = MAX1((3 * qi4 * qi4) >> 7);
-    s.l_i16 = MAX1(3 * qi16 * qi16);
-    s.l_uv = MAX1((3 * quv * quv) >> 6);
-    s.l_mode = MAX1((qi4 * qi4) >> 7);
-#undef MAX1
-    s.tlambda = (50 * qi4) >> 5;
-    s.quant_index = qi;
-    s.quantizer_level = delta;
-}
-
-// Consumes the frame's alpha histogram and clears it for the next launch of
-// k_analysis4 (zeroed once at pipeline creation; no per-launch memset blit).
-extern "C" __global__ void k_segments(uint32_t* __restrict__ histo, const ZwFrameParams* __restrict__ tmpl,
-                                      ZwFrameParams* __restrict__ params, int nframes)
-{
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= nframes) return;
-    ZwFrameParams P = *tmpl;
-    const int base = P.base_qi;
-    const int nmb = P.mbw * P.mbh;
-    for (int i = 0; i < 4; i++) segment_init(P.seg[i], base, 0);
-    for (int i = 0; i < 256; i++) P.seg_map_lut[i] = 0;
-    P.seg_probs[0] = P.seg_probs[1] = P.seg_probs[2] = 255;
-    P.seg_enabled = 0;
-    P.seg_update_map = 0;
-    if (nmb >= 256) {
-        const uint32_t* H = histo + (size_t)f * 256;
-        uint8_t centers[4] = {0, 0, 0, 0};
-        uint8_t* map = P.seg_map_lut;
-        int min_a = 0, max_a = 255;
-        for (int n = 0; n < 256; n++)
-            if (H[n] > 0) { min_a = n; break; }
-        for (int n = 255; n >= min_a; n--)
-            if (H[n] > 0) { max_a = n; break; }
-        int range = max_a > min_a ? max_a - min_a : 0;
-        for (int k = 0; k < 4; k++) centers[k] = (uint8_t)(min_a + ((1 + 2 * k) * range) / 8);
-        uint32_t accum[4], dacc[4];
-        int wa = 0;
-        uint32_t tw = 0;
-        for (int it = 0; it < 6; it++) {
-            for (int i = 0; i < 4; i++) accum[i] = dacc[i] = 0;
-            int cc = 0;
-            for (int a = min_a; a <= max_a; a++) {
-                if (H[a] > 0) {
-                    while (cc + 1 < 4) {
-                        int dc = iabs(a - centers[cc]), dn = iabs(a - centers[cc + 1]);
-                        if (dn < dc) cc++;
-                        else break;
-                    }
-                    map[a] = (uint8_t)cc;
-                    dacc[cc] += (uint32_t)a * H[a];
-                    accum[cc] += H[a];
-                }
-            }
-            int displaced = 0;
-            wa = 0;
-            tw = 0;
-            for (int n = 0; n < 4; n++) {
-                if (accum[n] > 0) {
-                    uint8_t nc = (uint8_t)((dacc[n] + accum[n] / 2) / accum[n]);
-                    displaced += iabs(centers[n] - nc);
-                    centers[n] = nc;
-                    wa += (int)nc * (int)accum[n];
-                    tw += accum[n];
-                }
-            }
-            if (displaced < 5) break;
-        }
-        int mid = tw > 0 ? (wa + (int)tw / 2) / (int)tw : 128;
-        int minc = centers[0], maxc = centers[0];
-        for (int i = 1; i < 4; i++) {
-            minc = min(minc, (int)centers[i]);
-            maxc = max(maxc, (int)centers[i]);
-        }
-        int rng = maxc == minc ? 1 : maxc - minc;
-        for (int s = 0; s < 4; s++) {
-            int ta = 255 * ((int)centers[s] - mid) / rng;
-            ta = ta < -127 ? -127 : (ta > 127 ? 127 : ta);
-            int sq = segment_quant(base, ta, 50);
-            int delta = (int)(int8_t)((int8_t)sq - (int8_t)base);
-            segment_init(P.seg[s], sq, delta);
-        }
-        uint32_t cnt[4] = {0, 0, 0, 0};
-        for (int a = 0; a < 256; a++) cnt[map[a]] += H[a];
-        uint32_t t01 = cnt[0] + cnt[1], t23 = cnt[2] + cnt[3];
-#define GETP(a, b) ((a) + (b) == 0 ? 255 : (uint8_t)((255 * (a) + ((a) + (b)) / 2) / ((a) + (b))))
-        P.seg_probs[0] = GETP(t01, t23);
-        P.seg_probs[1] = GETP(cnt[0], cnt[1]);
-        P.seg_probs[2] = GETP(cnt[2], cnt[3]);
-#undef GETP
-        P.seg_update_map = P.seg_probs[0] != 255 || P.seg_probs[1] != 255 || P.seg_probs[2] != 255;
-        P.seg_enabled = 1;
-    }
-    params[f] = P;
-    uint4* Hz = (uint4*)(histo + (size_t)f * 256);
-    for (int i = 0; i < 64; i++) Hz[i] = make_uint4(0u, 0u, 0u, 0u);
-}
 
 // ---------------------------------------------------------------------------
 // The encode pass.
@@ -915,13 +344,6 @@ extern "C" int zw_phase_cycles(unsigned long long* out, int reset)
     do {                \
         if (C.lane == 0) C.W->ph[k] += 1; \
     } while (0)
-#elif defined(ZW_ASM_MARKS)
-#define PH_COUNT(k) (void)0
-// ISA inspection builds: phase boundaries as assembly comments
-#define PH_START() asm volatile("; ZWMARK start" ::: "memory")
-#define PH_RESET() (void)0
-#define PH_MARK(k) asm volatile("; ZWMARK " #k ::: "memory")
-#define PH_MARK_L(k, ln, ps) asm volatile("; ZWMARK " #k ::: "memory")
 #else
 #define PH_COUNT(k) (void)0
 #define PH_START() (void)0
@@ -3118,27 +2540,39 @@ DI void row_publish(int* prog, int val)
     __builtin_amdgcn_wave_barrier();
 }
 
+// Pass 1's chroma chain: two waves in the row-parallel kernels (the quad form,
+// one wave per plane), one in the batch kernels (the pair form).  The two-wave
+// chain bounds the row-parallel pass 1 (one 1080p frame: 27.7 -> 22.1 ms), and
+// those pass-1 workgroups then run two waves (the chain's two planes; two luma
+// rows elsewhere).  In the batch kernels a second chain wave costs a luma wave
+// and measured slower (34.4 -> 35.0 ms per 256 1080p frames).
 template <bool ROWS> struct ChainShape {
-    static constexpr int NCH = (ROWS ? ZW_UVQ_CHAIN_ROWS : ZW_UVQ_CHAIN_BATCH) ? 2 : 1;
+    static constexpr int NCH = ROWS ? 2 : 1;
 };
-#if ZW_PAIR_UNROLL
-#define ZW_PAIR_LOOP _Pragma("unroll")
-#else
-#define ZW_PAIR_LOOP _Pragma("nounroll")
-#endif
 template <int PASS> struct RowsShape {
     static constexpr int NW = PASS == 1 ? ChainShape<true>::NCH : 1;
+};
+// The waves of one encode kernel.
+template <int PASS, bool ROWS, int FP> struct EncShape {
+    static_assert(FP == 1 || (FP == 2 && !ROWS), "frame pairs: the batch kernels");
+    static constexpr bool PAIR = FP == 2;  // frame pairs: the workgroup encodes frames f and f + 1
+    static constexpr int NW = ROWS ? RowsShape<PASS>::NW : PassShape<PASS>::NW, WG = NW * 64;
+    static constexpr int NCH = PASS == 1 ? ChainShape<ROWS>::NCH : 0;  // chain waves (pass 1)
+    // pass 1's chroma chain waves: in frame pairs one per frame (the one-wave
+    // form), else NCH (the quad form's two waves in the row kernels)
+    static constexpr int NCW = PASS == 1 ? (PAIR ? 2 : NCH) : 0;
 };
 
 constexpr size_t a16(size_t v) { return (v + 15) & ~(size_t)15; }
 
-// The dynamic LDS of an encode workgroup: the sizes of its regions, read by
-// the kernel (encode_body carves the regions in the order of bytes()'s sum) and
-// by the host (bytes() sizes the launch, the widest encodable frame and whether
-// frame pairs fit).  Per frame of the workgroup: the tables (sT), the frame's
-// 4 segments (sS), the alpha map (sL) and the top rows (sy, su, sv, sc, sd);
-// per wave: WaveLds (sW) and, in frame pairs, a second MbLds (sM); then the
-// progress words and the two-wave chroma chain's exchange words.
+// The dynamic LDS of an encode workgroup: the sizes of its regions and, in
+// map(), their order.  The kernel takes every region pointer from map() and
+// the host takes its end (bytes(): the launch's size, the widest encodable
+// frame, whether frame pairs fit), so a region cannot be sized and not carved,
+// or carved and not sized.  Per frame of the workgroup: the tables (sT), the
+// frame's 4 segments (sS), the alpha map (sL) and the top rows (sy, su, sv, sc,
+// sd); per wave: WaveLds (sW) and, in frame pairs, a second MbLds (sM); then
+// the progress words and the two-wave chroma chain's exchange words.
 //
 // Of the frame-wide row arrays (top_y, top_u, top_v, top_c, top_derr) the batch
 // kernels (one workgroup per frame) keep all; in the row-parallel kernels the
@@ -3159,13 +2593,219 @@ struct EncLds {
         sc = all ? (((size_t)mbw * 12 + 15) & ~(size_t)15) : 0;
         sd = all || chain ? (((size_t)mbw * 4 + 15) & ~(size_t)15) : 0;
     }
-    __host__ __device__ size_t bytes(int nw, int fp) const
+    // Byte offset of every region (of its first frame's or wave's share) and the end.
+    struct Map {
+        size_t T, S, lut, W, M2, progress, xch, top_y, top_u, top_v, top_c, top_derr, end;
+    };
+    __host__ __device__ Map map(int nw, int fp) const
     {
-        return sT * fp + sS * fp + sL * fp + sW * nw + (fp == 2 ? sM * nw : 0) + sProgress + sXch +
-               (sy + su + sv + sc + sd) * fp;
+        Map m;
+        size_t o = 0;
+        auto region = [&o](size_t n) {
+            const size_t at = o;
+            o += n;
+            return at;
+        };
+        m.T = region(sT * fp);
+        m.S = region(sS * fp);
+        m.lut = region(sL * fp);
+        m.W = region(sW * nw);
+        m.M2 = region(fp == 2 ? sM * nw : 0);
+        m.progress = region(sProgress);
+        m.xch = region(sXch);
+        m.top_y = region(sy * fp);
+        m.top_u = region(su * fp);
+        m.top_v = region(sv * fp);
+        m.top_c = region(sc * fp);
+        m.top_derr = region(sd * fp);
+        m.end = o;
+        return m;
     }
+    __host__ __device__ size_t bytes(int nw, int fp) const { return map(nw, fp).end; }
 };
 static_assert(NW_MAX * sizeof(int) <= 64, "the progress words");
+
+// What the waves of a workgroup share: the launch, the carved LDS (of the
+// per-frame regions the first frame's share: frame_lds steps to a frame), the
+// wave's own LDS and, in the row-parallel kernels, the frame's row state in
+// global memory.
+struct EncWg {
+    const EncArgs* a;
+    const EncLds L;
+    int f, nf;  // the workgroup's first frame and its frames (frame pairs: 2, the odd last workgroup 1)
+    int wv;
+    LdsTables* T;
+    ZwSegment* Sl;     // the frame's 4 segments (matrices, lambdas, sharpening)
+    uint8_t* seg_lut;  // alpha -> segment (zeros when segmentation is off)
+    WaveLds* W;
+    MbLds* M2;         // frame pairs: the wave's per-MB state of the second frame
+    int* progress;
+    int *xch, *xflag;  // two-wave chroma chain: [plane][2][12] exchange words, then 2 flags
+    uint8_t *top_y, *top_u, *top_v;
+    uint8_t* top_c;    // [mbw][12]: y2, y[4], u[2], v[2]
+    int8_t* top_derr;  // [mbw][4]
+    // row-parallel kernels: the launch's error word, the frame's ticket and
+    // progress words and its row arrays (RowsLayout)
+    int *rerr, *rsync;
+    uint8_t *gty, *gtu, *gtv, *gtc, *gtd;
+    __device__ EncWg(const EncArgs& a_, bool rows, int pass) : a(&a_), L(a_.mbw, rows, pass) {}
+};
+
+template <int PASS, bool ROWS, int FP> DI EncWg enc_carve(const EncArgs& a, uint8_t* smem)
+{
+    using SH = EncShape<PASS, ROWS, FP>;
+    EncWg G(a, ROWS, PASS);
+    const EncLds::Map at = G.L.map(SH::NW, FP);
+    G.f = ROWS ? blockIdx.y : blockIdx.x * FP;
+    G.nf = SH::PAIR ? min(2, a.nframes - G.f) : 1;
+    G.wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    G.T = (LdsTables*)(smem + at.T);
+    G.Sl = (ZwSegment*)(smem + at.S);
+    G.seg_lut = smem + at.lut;
+    G.W = (WaveLds*)(smem + at.W + G.L.sW * G.wv);
+    G.M2 = (MbLds*)(smem + at.M2) + G.wv;
+    G.progress = (int*)(smem + at.progress);
+    G.xch = (int*)(smem + at.xch);
+    G.xflag = G.xch + 48;
+    G.top_y = smem + at.top_y;
+    G.top_u = smem + at.top_u;
+    G.top_v = smem + at.top_v;
+    G.top_c = smem + at.top_c;
+    G.top_derr = (int8_t*)(smem + at.top_derr);
+    const RowsLayout RL(a.mbw, a.mbh);
+    uint8_t* rb = ROWS ? a.rows + ZW_ROWS_HDR + (size_t)G.f * RL.frame : nullptr;
+    G.rerr = ROWS ? (int*)a.rows : nullptr;
+    G.rsync = (int*)rb;
+    G.gty = ROWS ? rb + RL.ty : nullptr;
+    G.gtu = ROWS ? rb + RL.tu : nullptr;
+    G.gtv = ROWS ? rb + RL.tv : nullptr;
+    G.gtc = ROWS ? rb + RL.tc : nullptr;
+    G.gtd = ROWS ? rb + RL.td : nullptr;
+    return G;
+}
+
+// One frame's share of the workgroup's LDS, and the frame's settings.
+struct FrameLds {
+    LdsTables* T;
+    ZwSegment* Sl;
+    uint8_t* seg_lut;
+    uint8_t *top_y, *top_u, *top_v, *top_c;
+    int8_t* top_derr;
+    const ZwFrameParams* P;
+    int f;       // frame of the launch
+    int method;  // per-frame encoder settings (a launch's frames normally share them)
+    bool trel;
+    // without trellis (and without the pass-2 I4 dump) the final I4 blocks are
+    // the search's winners, which the search leaves in C.M->lev / C.M->ws
+    bool keep_i4;
+};
+// Share fr of the workgroup.  (The odd last workgroup of a pair launch has a
+// second share and no second frame: that share carries the first frame's
+// number and settings, and nothing is encoded from it.)
+template <int PASS> DI FrameLds frame_lds(const EncWg& G, int fr)
+{
+    const EncLds& L = G.L;
+    FrameLds F;
+    F.T = (LdsTables*)((uint8_t*)G.T + L.sT * fr);
+    F.Sl = (ZwSegment*)((uint8_t*)G.Sl + L.sS * fr);
+    F.seg_lut = G.seg_lut + L.sL * fr;
+    F.top_y = G.top_y + L.sy * fr;
+    F.top_u = G.top_u + L.su * fr;
+    F.top_v = G.top_v + L.sv * fr;
+    F.top_c = G.top_c + L.sc * fr;
+    F.top_derr = G.top_derr + L.sd * fr;
+    F.f = G.f + (fr < G.nf ? fr : 0);
+    F.P = G.a->params + F.f;
+    F.method = __builtin_amdgcn_readfirstlane(F.P->method);
+    F.trel = PASS == 2 && __builtin_amdgcn_readfirstlane(F.P->do_trellis);
+    F.keep_i4 = !F.trel && (PASS == 1 || G.a->dbg == nullptr);
+    return F;
+}
+// Point C at MB (mbx, mby) of that frame; M: the wave's per-MB state for it.
+DI void ctx_enter(Ctx& C, const FrameLds& F, MbLds* M, int mbx, int mby)
+{
+    C.f = F.f;
+    C.P = F.P;
+    C.T = F.T;
+    C.Sl = F.Sl;
+    C.top_y = F.top_y;
+    C.top_u = F.top_u;
+    C.top_v = F.top_v;
+    C.top_c = F.top_c;
+    C.top_derr = F.top_derr;
+    C.M = M;
+    C.method = F.method;
+    C.mbx = mbx;
+    C.mby = mby;
+    C.oy = mbx * 16;
+    C.oc = mbx * 8;
+    C.ocx = mbx * 12;
+    C.od = mbx * 4;
+    C.sY = M->sy;
+    C.sU = M->su;
+    C.sV = M->sv;
+}
+
+// Fill the workgroup's shared state (each of its frames), then barrier.
+template <int PASS, bool ROWS, int FP> DI void enc_fill(const EncWg& G, bool chain_wg)
+{
+    constexpr int NW = EncShape<PASS, ROWS, FP>::NW, WG = NW * 64;
+    const EncArgs& a = *G.a;
+    const int mbw = a.mbw;
+#pragma unroll
+    for (int fr = 0; fr < FP; fr++) {
+        if (fr >= G.nf) break;
+        const FrameLds F = frame_lds<PASS>(G, fr);
+        const int ff = F.f;
+        const ZwFrameParams* Pf = F.P;
+        LdsTables* Tf = F.T;
+        for (int i = threadIdx.x; i < (int)(sizeof(Tf->lc) / 2); i += WG)
+            (&Tf->lc[0][0][0][0])[i] = a.lcost ? (&a.lcost[ff].lc[0][0][0][0])[i] : 0;
+        for (int i = threadIdx.x; i < 96; i += WG) {
+            (&Tf->eob[0][0][0])[i] = a.lcost ? (&a.lcost[ff].eob[0][0][0])[i] : 0;
+            (&Tf->init[0][0][0])[i] = a.lcost ? (&a.lcost[ff].init[0][0][0])[i] : 0;
+        }
+        for (int i = threadIdx.x; i < 4 * 8 * 3 * 11; i += WG) (&Tf->probs[0][0][0][0])[i] = (&Pf->probs[0][0][0][0])[i];
+        static_assert(sizeof(ZwSegment) % 4 == 0, "segment copy by dwords");
+        for (int i = threadIdx.x; i < (int)(4 * sizeof(ZwSegment) / 4); i += WG)
+            ((uint32_t*)F.Sl)[i] = ((const uint32_t*)Pf->seg)[i];
+        for (int i = threadIdx.x; i < 256; i += WG) F.seg_lut[i] = Pf->seg_enabled ? Pf->seg_map_lut[i] : 0;
+        load_static_tables(Tf, threadIdx.x, WG, &Pf->probs[0][0][0][0]);
+        if (!ROWS || chain_wg) {
+            if (!ROWS) {
+                for (int i = threadIdx.x; i < mbw * 16 + 48; i += WG) F.top_y[i] = 127;
+                for (int i = threadIdx.x; i < mbw * 12; i += WG) F.top_c[i] = 0;
+            }
+            for (int i = threadIdx.x; i < mbw * 8 + 48; i += WG) {
+                F.top_u[i] = 127;
+                F.top_v[i] = 127;
+            }
+            for (int i = threadIdx.x; i < mbw * 4; i += WG)
+                F.top_derr[i] = PASS == 2 ? a.derr[(size_t)ff * mbw * 4 + i] : 0;
+        }
+    }
+    if (threadIdx.x < NW) G.progress[threadIdx.x] = -1;
+    if (threadIdx.x < 2) G.xflag[threadIdx.x] = 0;
+    if (ROWS && (threadIdx.x & 63) < 12) G.W->win_c[threadIdx.x & 63] = 0;  // pass 1: the complexity contexts stay zero
+    __syncthreads();
+}
+
+// Profiling builds: the wave's phase counters, cleared at the start of the
+// kernel and added to the global ones once at its end.
+DI void ph_init(const EncWg& G, int lane)
+{
+#ifdef ZW_PHASE_PROF
+    if (lane < ZW_PH_N) G.W->ph[lane] = 0;
+    wsync();
+#endif
+}
+template <int PASS> DI void ph_flush(const EncWg& G, int lane)
+{
+#ifdef ZW_PHASE_PROF
+    if (lane < ZW_PH_N) atomicAdd(&zw_phase_cycles_dev[PASS - 1][lane], G.W->ph[lane]);
+    if (lane < ZW_PH_N) atomicAdd(&zw_wave_cycles_dev[PASS - 1][G.wv][lane], G.W->ph[lane]);
+#endif
+}
 
 // A wave starts an MB row: the left borders and contexts of its first MB.
 DI void row_start(MbLds* M, int lane)
@@ -3200,264 +2840,475 @@ template <int PASS> DI void luma_issue_prio(const int* progress, int prevw, int 
 #endif
 }
 
-template <int PASS, bool ROWS, int FP = 1>
-__device__ __forceinline__ void encode_body(const EncArgs& a)
+// ---------------------------------------------------------------------------
+// Everything of an MB after its searches, in three steps: the final luma
+// transform, the final chroma transform (pass 2), and the stores.  What the
+// transforms hand on is one word each: the blocks' has-coefficients flags
+// (luma bits 0..15, chroma bits 0..7) and above them the simple-quant "any
+// nonzero" flag (luma bit 16, chroma bit 8).
+// ---------------------------------------------------------------------------
+DI uint32_t mb_luma(Ctx& C, int lm, bool i4reuse, uint32_t i4nz, bool trel)
 {
-    constexpr int NW = ROWS ? RowsShape<PASS>::NW : PassShape<PASS>::NW, WG = NW * 64;
-    constexpr int NCH = PASS == 1 ? ChainShape<ROWS>::NCH : 0;  // chain waves (pass 1)
-    constexpr bool PAIR = FP == 2;  // frame pairs: the workgroup encodes frames f and f + 1
-    static_assert(FP == 1 || (FP == 2 && !ROWS), "frame pairs: the batch kernels");
-    // pass 1's chroma chain waves: in frame pairs one per frame (the one-wave
-    // form), else NCH (the quad form's two waves in the row kernels)
-    constexpr int NCW = PASS == 1 ? (PAIR ? 2 : NCH) : 0;
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const int f = ROWS ? blockIdx.y : blockIdx.x * FP;
-    const int nf = PAIR ? min(2, a.nframes - f) : 1;  // frames of this workgroup
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int mbw = a.mbw, mbh = a.mbh;
-    const ZwFrameParams* P = a.params + f;
-    // carve LDS
-    // (the regions in the order of EncLds::bytes())
-    const EncLds L(mbw, ROWS, PASS);
-    size_t off = 0;
-    // (per frame of the workgroup: the tables, segments, alpha map and the top rows)
-    LdsTables* T = (LdsTables*)(smem + off);
-    off += L.sT * FP;
-    ZwSegment* Sl = (ZwSegment*)(smem + off);  // the frame's 4 segments (matrices, lambdas, sharpening)
-    off += L.sS * FP;
-    uint8_t* seg_lut = smem + off;  // alpha -> segment (zeros when segmentation is off)
-    off += L.sL * FP;
-    WaveLds* Wall = (WaveLds*)(smem + off);
-    off += L.sW * NW;
-    MbLds* Mall2 = (MbLds*)(smem + off);  // frame pairs: the second frame's per-MB state
-    off += PAIR ? L.sM * NW : 0;
-    int* progress = (int*)(smem + off);
-    off += L.sProgress;
-    int* xch = (int*)(smem + off);  // two-wave chroma chain: [plane][2][12] exchange words, then 2 flags
-    int* xflag = xch + 48;
-    off += L.sXch;
-    uint8_t* top_y = smem + off;
-    off += L.sy * FP;
-    uint8_t* top_u = smem + off;
-    off += L.su * FP;
-    uint8_t* top_v = smem + off;
-    off += L.sv * FP;
-    uint8_t* top_c = smem + off;  // [mbw][12]: y2, y[4], u[2], v[2]
-    off += L.sc * FP;
-    int8_t* top_derr = (int8_t*)(smem + off);  // [mbw][4]
-    WaveLds* W = (WaveLds*)((uint8_t*)Wall + L.sW * wv);
-    // row-parallel: is this workgroup pass 1's chroma chain (it keeps the
-    // frame-wide top_u/v/derr in LDS), and the frame's global row state
-    const bool chain_wg = PASS == 1 && (ROWS ? blockIdx.x == 0 : wv < NCW);
-    const RowsLayout RL(mbw, mbh);
-    uint8_t* rb = ROWS ? a.rows + ZW_ROWS_HDR + (size_t)f * RL.frame : nullptr;
-    int* rerr = ROWS ? (int*)a.rows : nullptr;
-    int* rsync = (int*)rb;
-
-    // init shared state (each frame of the workgroup)
+    int ynz[16];
+    uint32_t r = (uint32_t)(final_luma(C, lm, trel, ynz, i4reuse ? (int)i4nz : -1) != 0) << 16;
 #pragma unroll
-    for (int fr = 0; fr < FP; fr++) {
-        if (fr >= nf) break;
-        const int ff = f + fr;
-        const ZwFrameParams* Pf = a.params + ff;
-        LdsTables* Tf = (LdsTables*)((uint8_t*)T + L.sT * fr);
-        ZwSegment* Sf = (ZwSegment*)((uint8_t*)Sl + L.sS * fr);
-        uint8_t* lut = seg_lut + L.sL * fr;
-        for (int i = threadIdx.x; i < (int)(sizeof(Tf->lc) / 2); i += WG)
-            (&Tf->lc[0][0][0][0])[i] = a.lcost ? (&a.lcost[ff].lc[0][0][0][0])[i] : 0;
-        for (int i = threadIdx.x; i < 96; i += WG) {
-            (&Tf->eob[0][0][0])[i] = a.lcost ? (&a.lcost[ff].eob[0][0][0])[i] : 0;
-            (&Tf->init[0][0][0])[i] = a.lcost ? (&a.lcost[ff].init[0][0][0])[i] : 0;
-        }
-        for (int i = threadIdx.x; i < 4 * 8 * 3 * 11; i += WG) (&Tf->probs[0][0][0][0])[i] = (&Pf->probs[0][0][0][0])[i];
-        static_assert(sizeof(ZwSegment) % 4 == 0, "segment copy by dwords");
-        for (int i = threadIdx.x; i < (int)(4 * sizeof(ZwSegment) / 4); i += WG)
-            ((uint32_t*)Sf)[i] = ((const uint32_t*)Pf->seg)[i];
-        for (int i = threadIdx.x; i < 256; i += WG) lut[i] = Pf->seg_enabled ? Pf->seg_map_lut[i] : 0;
-        load_static_tables(Tf, threadIdx.x, WG, &Pf->probs[0][0][0][0]);
-        if (!ROWS || chain_wg) {
-            uint8_t* ty = top_y + L.sy * fr;
-            uint8_t* tu = top_u + L.su * fr;
-            uint8_t* tv = top_v + L.sv * fr;
-            uint8_t* tcx = top_c + L.sc * fr;
-            int8_t* td = top_derr + L.sd * fr;
-            if (!ROWS) {
-                for (int i = threadIdx.x; i < mbw * 16 + 48; i += WG) ty[i] = 127;
-                for (int i = threadIdx.x; i < mbw * 12; i += WG) tcx[i] = 0;
+    for (int k = 0; k < 16; k++) r |= (uint32_t)(ynz[k] != 0) << k;
+    return r;
+}
+DI uint32_t mb_chroma(Ctx& C, int cm)
+{
+    int uvnz[8];
+    uint32_t r = (uint32_t)(final_chroma(C, cm, C.top_derr + C.od, uvnz) != 0) << 8;
+#pragma unroll
+    for (int k = 0; k < 8; k++) r |= (uint32_t)(uvnz[k] != 0) << k;
+    return r;
+}
+// the stores: the complexity contexts (pass 2), the levels, the MB record
+// and the borders (the chroma borders only if the caller has not stored them)
+template <int PASS> DI void mb_finish(Ctx& C, int lm, int cm, uint32_t lres, uint32_t cres, bool chroma_borders)
+{
+    const EncArgs& a = *C.a;
+    const int lane = C.lane, mbw = a.mbw;
+    const size_t nmb = (size_t)mbw * a.mbh;
+    int ynz[16], uvnz[8];
+#pragma unroll
+    for (int k = 0; k < 16; k++) ynz[k] = (int)((lres >> k) & 1u);
+#pragma unroll
+    for (int k = 0; k < 8; k++) uvnz[k] = (int)((cres >> k) & 1u);
+    const int lnz = (int)((lres >> 16) & 1u), cnz = (int)((cres >> 8) & 1u);
+    ZwMbOut* o = a.out + (size_t)C.f * nmb + (size_t)C.mby * mbw + C.mbx;
+    if (PASS == 2) {
+        const int skip = !(lnz | cnz);
+        // complexity (encode_residual_data semantics / skip clearing)
+        if (lane == 0) {
+            uint8_t* tc = C.top_c + C.ocx;
+            uint8_t* lc = C.M->left_c;
+            if (skip) {
+                for (int k = 1; k < 9; k++) tc[k] = lc[k] = 0;
+                if (lm != 4) tc[0] = lc[0] = 0;
+            } else {
+                if (lm != 4) {
+                    int y2nz = 0;
+                    for (int n = 0; n < 16; n++) y2nz |= C.M->lev[16][n] != 0;
+                    tc[0] = lc[0] = (uint8_t)y2nz;
+                }
+                for (int x = 0; x < 4; x++) tc[1 + x] = (uint8_t)ynz[12 + x];
+                for (int y = 0; y < 4; y++) lc[1 + y] = (uint8_t)ynz[y * 4 + 3];
+                tc[5] = (uint8_t)uvnz[2];
+                tc[6] = (uint8_t)uvnz[3];
+                lc[5] = (uint8_t)uvnz[1];
+                lc[6] = (uint8_t)uvnz[3];
+                tc[7] = (uint8_t)uvnz[6];
+                tc[8] = (uint8_t)uvnz[7];
+                lc[7] = (uint8_t)uvnz[5];
+                lc[8] = (uint8_t)uvnz[7];
             }
-            for (int i = threadIdx.x; i < mbw * 8 + 48; i += WG) {
-                tu[i] = 127;
-                tv[i] = 127;
-            }
-            for (int i = threadIdx.x; i < mbw * 4; i += WG) td[i] = PASS == 2 ? a.derr[(size_t)ff * mbw * 4 + i] : 0;
+            o->skip = (uint8_t)skip;
+            o->chroma_mode = (uint8_t)cm;
         }
-    }
-    if (threadIdx.x < NW) progress[threadIdx.x] = -1;
-    if (threadIdx.x < 2) xflag[threadIdx.x] = 0;
-    if (ROWS && lane < 12) W->win_c[lane] = 0;  // pass 1: the complexity contexts stay zero
-    __syncthreads();
-
-    Ctx C;
-    C.a = &a;
-    C.P = P;
-    C.T = T;
-    C.W = W;
-    C.M = &W->mb;
-    C.lane = lane;
-    C.f = f;
-    C.Sl = Sl;
-    C.method = __builtin_amdgcn_readfirstlane(P->method);
-    C.top_y = top_y;
-    C.top_u = top_u;
-    C.top_v = top_v;
-    C.top_c = top_c;
-    C.top_derr = top_derr;
-    C.oy = C.oc = C.ocx = C.od = 0;
-    const bool trel = PASS == 2 && __builtin_amdgcn_readfirstlane(P->do_trellis);
-    // without trellis (and without the pass-2 I4 dump) the final I4 blocks are
-    // the search's winners, which the search leaves in C.M->lev / C.M->ws
-    const bool keep_i4 = !trel && (PASS == 1 || a.dbg == nullptr);
-    const size_t nmb = (size_t)mbw * mbh;
-#ifdef ZW_PHASE_PROF
-    if (lane < ZW_PH_N) W->ph[lane] = 0;
-    wsync();
-    auto ph_flush = [&]() {
-        if (lane < ZW_PH_N) atomicAdd(&zw_phase_cycles_dev[PASS - 1][lane], W->ph[lane]);
-        if (lane < ZW_PH_N) atomicAdd(&zw_wave_cycles_dev[PASS - 1][wv][lane], W->ph[lane]);
-    };
-#else
-    auto ph_flush = []() {};
-#endif
-
-    if (chain_wg) {
-        // ---- pass-1 chroma raster chain ---- (issue priority: see ZW_CHAIN_PRIO)
-        __builtin_amdgcn_s_setprio(ZW_CHAIN_PRIO);
-        // frame pairs: chain wave k works frame f + k
-        const int cfr = PAIR ? wv : 0;
-        // (the odd last workgroup of a pair launch: chain wave 1 has no frame,
-        // only its luma rows; it points at frame f and runs no chain row)
-        const bool has_chain = !PAIR || cfr < nf;
-        const int fc = f + (has_chain ? cfr : 0);
-        const uint8_t* const lutc = seg_lut + L.sL * cfr;
-        int8_t* const tdc = top_derr + L.sd * cfr;
-        if (PAIR) {
-            C.f = fc;
-            C.P = a.params + fc;
-            C.T = (const LdsTables*)((const uint8_t*)T + L.sT * cfr);
-            C.Sl = (const ZwSegment*)((const uint8_t*)Sl + L.sS * cfr);
-            C.top_u = top_u + L.su * cfr;
-            C.top_v = top_v + L.sv * cfr;
-            C.top_derr = tdc;
-            C.method = __builtin_amdgcn_readfirstlane(C.P->method);
-        }
-        if (lane < 4) C.M->left_derr[lane] = 0;
-        if (NCH == 2 && !PAIR) {
-            // quad form: wave 0 the U plane, wave 1 the V plane
-            const int pl = wv;
-            UvQ U;
-            U.pl = pl;
-            U.w = W->cu;
-            U.sp = C.M->su;
-            U.top = pl ? top_v : top_u;
-            U.left = C.M->left_u;
-            const uint8_t* const P0 = (pl ? a.V : a.U) + (size_t)f * a.csz;
-            const int cs = mbw * 8;
-            auto fetch_uv = [&](int mbx, int mby) {
-                MbFetch r;
-                r.y = lane < 16 ? *(const uint32_t*)(P0 + (size_t)(mby * 8 + (lane >> 1)) * cs + mbx * 8 + (lane & 1) * 4)
-                                : 0u;
-                r.c = 0;
-                r.alpha = a.alpha[(size_t)f * nmb + (size_t)mby * mbw + mbx];
-                return r;
-            };
-            C.ys = mbw * 16;
-            C.cs = cs;
-            MbFetch nx = fetch_uv(0, 0);
-            int seq = 0;
-            for (int mby = 0; mby < mbh; mby++) {
-                if (lane < 12) C.M->left_u[lane] = 129;
-                wsync();
-                for (int mbx = 0; mbx < mbw; mbx++) {
-                    PH_START();
-                    const int lane = opaque_lane(threadIdx.x & 63);
-                    C.lane = lane;
-                    const MbFetch cur = nx;
-                    if (mbx + 1 < mbw) nx = fetch_uv(mbx + 1, mby);
-                    else if (mby + 1 < mbh) nx = fetch_uv(0, mby + 1);
-                    C.mbx = mbx;
-                    C.mby = mby;
-                    if (lane < 16) ((uint32_t*)C.M->su)[lane] = cur.y;
-                    wsync();
-                    const int seg = __builtin_amdgcn_readfirstlane((int)seg_lut[cur.alpha]);
-                    C.seg = seg;
-                    C.S = C.Sl + seg;
-                    uvq_border(C, U);
-                    const int cm = uvq_pick(C, U, xch, xflag, ++seq);
-                    PH_MARK(8);
-                    uvq_final(C, U, cm, top_derr + mbx * 4);
-                    PH_MARK(9);
-                    uvq_store_borders(C, U);
-                    ZwMbOut* o = a.out + (size_t)f * nmb + (size_t)mby * mbw + mbx;
-                    if (pl == 0 && lane == 0) o->chroma_mode = (uint8_t)cm;
-                    write_levels(C, 17 + 4 * pl, 4, false);
-                    wsync();
+        if (chroma_borders) store_chroma_borders(C);
+        write_levels(C, 0, 25, skip);
+        if (a.sizes) {
+            // the packed record size k_pack_size would compute from these
+            // levels: header, eob bytes and every block's levels up to its eob
+            int e = 0;
+            if (lane < 25 && !skip) {
+                const uint32_t* lw = (const uint32_t*)C.M->lev[lane];
+#pragma unroll
+                for (int q = 0; q < 8; q++) {
+                    const uint32_t v = lw[q];
+                    e = (v >> 16) ? 2 * q + 2 : ((v & 0xffffu) ? 2 * q + 1 : e);
                 }
             }
-            for (int i = lane; i < mbw * 2; i += 64) {
-                const int j = (i >> 1) * 4 + pl * 2 + (i & 1);
-                a.derr[(size_t)f * mbw * 4 + j] = top_derr[j];
-            }
-            ph_flush();
-            return;
+            // lanes 0..24 hold the eobs: DPP sums per 16-lane row, rows 0 and 1 added
+            const int r16 = red16(e);
+            const int es = __builtin_amdgcn_readlane(r16, 0) + __builtin_amdgcn_readlane(r16, 16);
+            if (lane == 0)
+                a.sizes[(size_t)C.f * nmb + (size_t)C.mby * mbw + C.mbx] = (uint32_t)(1 + (lm == 4 ? 8 : 0) + 25 + 2 * es);
         }
-        MbFetch nx = fetch_mb(&a, fc, lane, 0, 0);
-        for (int mby = 0; has_chain && mby < mbh; mby++) {
-            if (lane < 12) {
-                C.M->left_u[lane] = 129;
-                C.M->left_v[lane] = 129;
-            }
+    } else {
+        write_levels(C, 0, 17, false);
+        if (lane == 0) o->skip = 0;  // pass-1 skip is decided on the host from the levels
+    }
+    if (lane == 0) {
+        o->luma_mode = (uint8_t)lm;
+        o->segment = (uint8_t)C.seg;
+    }
+    if (lane < 16) o->bpred[lane] = lm == 4 ? C.M->modes[lane] : 0;
+    store_luma_borders(C);
+}
+template <int PASS> DI void mb_store(Ctx& C, int lm, int cm, bool i4reuse, uint32_t i4nz, bool trel)
+{
+    [[maybe_unused]] const int lane = C.lane;
+    PH_START();
+    const uint32_t lres = mb_luma(C, lm, i4reuse, i4nz, trel);
+    PH_MARK(4);
+    const uint32_t cres = PASS == 2 ? mb_chroma(C, cm) : 0u;
+    PH_MARK(5);
+    mb_finish<PASS>(C, lm, cm, lres, cres, true);
+}
+
+// ---------------------------------------------------------------------------
+// Pass 1's chroma raster chain, quad form (the row-parallel kernels): wave 0
+// the U plane, wave 1 the V plane.
+// ---------------------------------------------------------------------------
+template <int PASS> DI void chain_quad(const EncWg& G, Ctx& C)
+{
+    const EncArgs& a = *G.a;
+    const int mbw = a.mbw, mbh = a.mbh, f = G.f, lane = C.lane;
+    const size_t nmb = (size_t)mbw * mbh;
+    if (lane < 4) C.M->left_derr[lane] = 0;
+    const int pl = __builtin_amdgcn_readfirstlane(G.wv);  // (wave-uniform: see luma_pairs)
+    UvQ U;
+    U.pl = pl;
+    U.w = G.W->cu;
+    U.sp = C.M->su;
+    U.top = pl ? G.top_v : G.top_u;
+    U.left = C.M->left_u;
+    const uint8_t* const P0 = (pl ? a.V : a.U) + (size_t)f * a.csz;
+    const int cs = mbw * 8;
+    auto fetch_uv = [&](int mbx, int mby) {
+        MbFetch r;
+        r.y = lane < 16 ? *(const uint32_t*)(P0 + (size_t)(mby * 8 + (lane >> 1)) * cs + mbx * 8 + (lane & 1) * 4) : 0u;
+        r.c = 0;
+        r.alpha = a.alpha[(size_t)f * nmb + (size_t)mby * mbw + mbx];
+        return r;
+    };
+    C.ys = mbw * 16;
+    C.cs = cs;
+    MbFetch nx = fetch_uv(0, 0);
+    int seq = 0;
+    for (int mby = 0; mby < mbh; mby++) {
+        if (lane < 12) C.M->left_u[lane] = 129;
+        wsync();
+        for (int mbx = 0; mbx < mbw; mbx++) {
+            PH_START();
+            const int lane = opaque_lane(threadIdx.x & 63);
+            C.lane = lane;
+            const MbFetch cur = nx;
+            if (mbx + 1 < mbw) nx = fetch_uv(mbx + 1, mby);
+            else if (mby + 1 < mbh) nx = fetch_uv(0, mby + 1);
+            C.mbx = mbx;
+            C.mby = mby;
+            if (lane < 16) ((uint32_t*)C.M->su)[lane] = cur.y;
             wsync();
-            for (int mbx = 0; mbx < mbw; mbx++) {
-                PH_START();
-                const int lane = opaque_lane(threadIdx.x & 63);
-                C.lane = lane;
-                const MbFetch cur = nx;
-                if (mbx + 1 < mbw) nx = fetch_mb(&a, fc, lane, mbx + 1, mby);
-                else if (mby + 1 < mbh) nx = fetch_mb(&a, fc, lane, 0, mby + 1);
-                setup_ctx(C, &a, lutc, W, mbx, mby, cur);
-                C.oc = mbx * 8;
-                C.ocx = mbx * 12;
-                build_chroma_border(C);
-                const int cm = pick_uv<PASS>(C);
-                PH_MARK(8);
-                int uvnz[8];
-                final_chroma(C, cm, tdc + mbx * 4, uvnz);
-                PH_MARK(9);
-                store_chroma_borders(C);
-                ZwMbOut* o = a.out + (size_t)fc * nmb + (size_t)mby * mbw + mbx;
-                if (lane == 0) o->chroma_mode = (uint8_t)cm;
-                write_levels(C, 17, 8, false);
+            const int seg = __builtin_amdgcn_readfirstlane((int)G.seg_lut[cur.alpha]);
+            C.seg = seg;
+            C.S = C.Sl + seg;
+            uvq_border(C, U);
+            const int cm = uvq_pick(C, U, G.xch, G.xflag, ++seq);
+            PH_MARK(8);
+            uvq_final(C, U, cm, G.top_derr + mbx * 4);
+            PH_MARK(9);
+            uvq_store_borders(C, U);
+            ZwMbOut* o = a.out + (size_t)f * nmb + (size_t)mby * mbw + mbx;
+            if (pl == 0 && lane == 0) o->chroma_mode = (uint8_t)cm;
+            write_levels(C, 17 + 4 * pl, 4, false);
+            wsync();
+        }
+    }
+    for (int i = lane; i < mbw * 2; i += 64) {
+        const int j = (i >> 1) * 4 + pl * 2 + (i & 1);
+        a.derr[(size_t)f * mbw * 4 + j] = G.top_derr[j];
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Pass 1's chroma raster chain, one-wave form (the batch kernels).  In frame
+// pairs chain wave k works frame f + k, and returns to take luma rows
+// (PairRowSchedule1, from the join row on).
+// ---------------------------------------------------------------------------
+template <int PASS, int FP> DI void chain_one(const EncWg& G, Ctx& C)
+{
+    const EncArgs& a = *G.a;
+    const int mbw = a.mbw, mbh = a.mbh, lane = C.lane;
+    const size_t nmb = (size_t)mbw * mbh;
+    const int cfr = FP == 2 ? G.wv : 0;
+    // (the odd last workgroup of a pair launch: chain wave 1 has no frame,
+    // only its luma rows; it runs no chain row)
+    const bool has_chain = cfr < G.nf;
+    const FrameLds F = frame_lds<PASS>(G, cfr);
+    ctx_enter(C, F, &G.W->mb, 0, 0);
+    if (lane < 4) C.M->left_derr[lane] = 0;
+    MbFetch nx = fetch_mb(&a, F.f, lane, 0, 0);
+    for (int mby = 0; has_chain && mby < mbh; mby++) {
+        if (lane < 12) {
+            C.M->left_u[lane] = 129;
+            C.M->left_v[lane] = 129;
+        }
+        wsync();
+        for (int mbx = 0; mbx < mbw; mbx++) {
+            PH_START();
+            const int lane = opaque_lane(threadIdx.x & 63);
+            C.lane = lane;
+            const MbFetch cur = nx;
+            if (mbx + 1 < mbw) nx = fetch_mb(&a, F.f, lane, mbx + 1, mby);
+            else if (mby + 1 < mbh) nx = fetch_mb(&a, F.f, lane, 0, mby + 1);
+            setup_ctx(C, &a, F.seg_lut, G.W, mbx, mby, cur);
+            C.oc = mbx * 8;
+            C.ocx = mbx * 12;
+            build_chroma_border(C);
+            const int cm = pick_uv<PASS>(C);
+            PH_MARK(8);
+            int uvnz[8];
+            final_chroma(C, cm, F.top_derr + mbx * 4, uvnz);
+            PH_MARK(9);
+            store_chroma_borders(C);
+            ZwMbOut* o = a.out + (size_t)F.f * nmb + (size_t)mby * mbw + mbx;
+            if (lane == 0) o->chroma_mode = (uint8_t)cm;
+            write_levels(C, 17, 8, false);
+            wsync();
+        }
+    }
+    for (int i = lane; has_chain && i < mbw * 4; i += 64) a.derr[(size_t)F.f * mbw * 4 + i] = F.top_derr[i];
+}
+
+// Both frames' Ctx for a stage that works MB (mbx, mby) of the two frames in
+// one pass of the wave (pick_i4_pair, final_luma_pair); seg0, seg1: the MBs'
+// segments.
+DI void ctx_pair(const Ctx& C, const FrameLds& F0, const FrameLds& F1, MbLds* const Mp[2], int mbx, int mby, int seg0,
+                 int seg1, Ctx& CA, Ctx& CB)
+{
+    CA = CB = C;
+    CA.lane = CB.lane = opaque_lane(threadIdx.x & 63);
+    ctx_enter(CA, F0, Mp[0], mbx, mby);
+    ctx_enter(CB, F1, Mp[1], mbx, mby);
+    CA.seg = seg0;
+    CB.seg = seg1;
+    CA.S = CA.Sl + seg0;
+    CB.S = CB.Sl + seg1;
+}
+
+// ---------------------------------------------------------------------------
+// The luma wavefront of frame pairs: every wave works MB row y of both frames
+// of the workgroup (which wave takes which row: RP below; in pass 1 the chain
+// waves arrive here after their chains and take rows from the join row on), MB
+// (x, y) of frame 0 and of frame 1 per iteration.  Both frames' rows advance
+// together, so one progress word per wave serves both.  The two MBs' I4
+// searches run in one wave (pick_i4_pair): lanes 0..31 frame 0, lanes 32..63
+// frame 1.  The other per-MB stages run in loops over the frames, and what an
+// MB's stages hand on goes through LDS (W->pst), not registers.
+//
+// The loops over the frames are unrolled: each stage is emitted twice, with a
+// constant frame index (as a two-trip loop, one copy of the code, pass 2
+// measured 30.26 against 29.80 ms per 256 1080p frames, pass 1 the same).
+// ---------------------------------------------------------------------------
+template <int PASS, int NW, int NCW> DI void luma_pairs(const EncWg& G, Ctx& C)
+{
+    const EncArgs& a = *G.a;
+    WaveLds* const W = G.W;
+    int* const progress = G.progress;
+    const int mbw = a.mbw, mbh = a.mbh, lane = C.lane;
+    // (wave-uniform, and said to be: a role is compiled as a function of its
+    // own before it becomes part of the kernel, and what it reads through G is
+    // then not known to be uniform; the frame count, the wave, its row and the
+    // wave of the row above steer every wait and otherwise end up in VGPRs)
+    const int nf = __builtin_amdgcn_readfirstlane(G.nf), wv = __builtin_amdgcn_readfirstlane(G.wv);
+    const FrameLds F[2] = {frame_lds<PASS>(G, 0), frame_lds<PASS>(G, 1)};
+    MbLds* const Mp[2] = {&W->mb, G.M2};
+    const int K = F[0].method <= 3 ? 3 : (F[0].method == 4 ? 4 : 10);
+    const bool same_k = nf == 1 || (F[1].method == F[0].method && F[1].trel == F[0].trel);
+    // pass 2: the waves take the rows in turn; pass 1: fewer rows for the
+    // luma waves beside a chain, and from the join row on the chain waves'
+    // too (PairRowSchedule1)
+    using RP = typename std::conditional<PASS == 1, PairRowSchedule1<NW, NCW>, RowSchedule<PASS, false, NW, NCW, true>>::type;
+    for (int mby = RP::first_row(wv, mbh); mby < mbh; mby = RP::next_row(wv, mby, mbh)) {
+#pragma unroll
+        for (int fr = 0; fr < 2; fr++) row_start(Mp[fr], lane);
+        wsync();
+        const int prevw = __builtin_amdgcn_readfirstlane(mby > 0 ? RP::wave_of_row(mby - 1, mbh) : 0);
+        auto wait_above = [&](int need) {
+            if (mby > 0) wait_row(progress, prevw, (mby - 1) * 65536 + need);
+        };
+        for (int mbx = 0; mbx < mbw; mbx++) {
+            PH_START();
+            const int lane = opaque_lane(threadIdx.x & 63);
+            C.lane = lane;
+            // point C at frame fr's MB (x, y)
+            auto enter = [&](int fr) {
+                // a fresh opaque lane per MB stage: lane-derived constants are
+                // recomputed, not held across the other frame's stages
+                C.lane = opaque_lane(threadIdx.x & 63);
+                ctx_enter(C, F[fr], Mp[fr], mbx, mby);
+            };
+            auto pst = [&](int fr, int k) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)W->pst[fr][k]); };
+            // the MB's segment and its Ctx fields, from the search's word
+            auto enter_seg = [&](int fr, uint32_t sm) {
+                enter(fr);
+                C.seg = (int)(sm >> 8);
+                C.S = C.Sl + C.seg;
+            };
+            wait_above(min(mbx + 1, mbw));
+            luma_issue_prio<PASS>(progress, prevw, mbx, mby, mbw);
+            PH_MARK(0);
+#pragma unroll
+            for (int fr = 0; fr < 2; fr++) {
+                if (fr >= nf) {
+                    if (lane == 0) W->pst[fr][0] = 0;  // (no frame 1: no search)
+                    continue;
+                }
+                enter(fr);
+                const MbFetch fm = fetch_mb(&a, C.f, lane, mbx, mby);
+                setup_ctx(C, &a, F[fr].seg_lut, W, mbx, mby, fm);
+                build_luma_border(C, 0);
+                int l_;
+                unsigned long long s_;
+                pick_i16<PASS>(C, l_, s_);
+                const bool n_ = C.method > 1 && (C.method >= 5 || s_ > 211ull * C.S->l_mode || l_ != 0);
+                if (lane == 0) {
+                    W->pst[fr][0] = (uint32_t)l_ | ((uint32_t)n_ << 4) | ((uint32_t)C.seg << 8);
+                    W->pst[fr][1] = (uint32_t)s_;
+                    W->pst[fr][2] = (uint32_t)(s_ >> 32);
+                    W->pst[fr][3] = 0;
+                }
                 wsync();
             }
+            wsync();
+            PH_MARK(1);
+            const uint32_t s0 = pst(0, 0), s1 = pst(1, 0);
+            const bool n0 = (s0 >> 4) & 1u, n1 = (s1 >> 4) & 1u;
+            if (n0 || n1) wait_above(min(mbx + 2, mbw));
+#pragma unroll
+            for (int fr = 0; fr < 2; fr++) {
+                if (!((pst(fr, 0) >> 4) & 1u)) continue;
+                enter(fr);
+                build_luma_border(C, 1);
+            }
+            PH_MARK(21);
+            if (K <= 4 && same_k && (n0 || n1)) {
+                Ctx CA, CB;
+                ctx_pair(C, F[0], F[1], Mp, mbx, mby, (int)(s0 >> 8), (int)(s1 >> 8), CA, CB);
+                const unsigned long long i0 = pst(0, 1) | ((unsigned long long)pst(0, 2) << 32);
+                const unsigned long long i1 = pst(1, 1) | ((unsigned long long)pst(1, 2) << 32);
+                uint32_t z0 = 0, z1 = 0;
+                const uint32_t r = pick_i4_pair<PASS>(CA, CB, i0, i1, n0, n1, F[0].keep_i4, z0, z1);
+                if (lane == 0) {
+                    W->pst[0][3] = (r & 1u) ? (z0 | 0x10000u) : 0u;
+                    W->pst[1][3] = (r & 2u) ? (z1 | 0x10000u) : 0u;
+                }
+            } else if (n0 || n1) {
+#pragma unroll
+                for (int fr = 0; fr < 2; fr++) {
+                    const uint32_t sm = pst(fr, 0);
+                    if (!((sm >> 4) & 1u)) continue;
+                    enter_seg(fr, sm);
+                    uint32_t z = 0;
+                    const bool w4 =
+                        pick_i4<PASS>(C, pst(fr, 1) | ((unsigned long long)pst(fr, 2) << 32), F[fr].keep_i4, z);
+                    if (lane == 0) W->pst[fr][3] = w4 ? (z | 0x10000u) : 0u;
+                }
+            }
+            wsync();
+            PH_MARK(2);
+            // The final stage.  Chroma first, frame by frame (pass 2; in pass 1
+            // the chain waves work it): W->uvc, cu and cv are the wave's, so a
+            // frame's final chroma and chroma borders are done before the other
+            // frame's search.  Its result replaces the I16 score in W->pst.
+            if (PASS == 2) {
+#pragma unroll
+                for (int fr = 0; fr < 2; fr++) {
+                    if (fr >= nf) continue;
+                    enter_seg(fr, pst(fr, 0));
+                    build_chroma_border(C);
+                    const int cm = pick_uv<PASS>(C);
+                    PH_MARK(3);
+                    const uint32_t cres = mb_chroma(C, cm);
+                    store_chroma_borders(C);
+                    if (lane == 0) W->pst[fr][1] = cres | ((uint32_t)cm << 9);
+                    PH_MARK(5);
+                }
+            }
+            // Luma: two I16 MBs in one pass of the wave (final_luma_pair),
+            // anything else (an I4 MB, the odd last workgroup, frames whose
+            // trellis settings differ) frame by frame.
+            const uint32_t w0 = pst(0, 3), w1 = pst(1, 3);
+            if (nf == 2 && !((w0 | w1) & 0x10000u) && F[0].trel == F[1].trel) {
+                Ctx CA, CB;
+                ctx_pair(C, F[0], F[1], Mp, mbx, mby, (int)(s0 >> 8), (int)(s1 >> 8), CA, CB);
+                uint32_t r0, r1;
+                final_luma_pair(CA, CB, (int)(s0 & 15u), (int)(s1 & 15u), F[0].trel, r0, r1);
+                if (lane == 0) {
+                    W->pst[0][2] = r0;
+                    W->pst[1][2] = r1;
+                }
+            } else {
+#pragma unroll
+                for (int fr = 0; fr < 2; fr++) {
+                    if (fr >= nf) continue;
+                    const uint32_t sm = pst(fr, 0), r4 = pst(fr, 3);
+                    enter_seg(fr, sm);
+                    const bool w4 = (r4 >> 16) & 1u;
+                    const uint32_t lres =
+                        mb_luma(C, w4 ? 4 : (int)(sm & 15u), w4 && F[fr].keep_i4, r4 & 0xffffu, F[fr].trel);
+                    if (lane == 0) W->pst[fr][2] = lres;
+                }
+                if (nf == 2) PH_COUNT(26);
+            }
+            wsync();
+            PH_MARK(4);
+            // the stores, frame by frame
+#pragma unroll
+            for (int fr = 0; fr < 2; fr++) {
+                if (fr >= nf) continue;
+                const uint32_t sm = pst(fr, 0), r4 = pst(fr, 3), cr = pst(fr, 1);
+                enter_seg(fr, sm);
+                const bool w4 = (r4 >> 16) & 1u;
+                mb_finish<PASS>(C, w4 ? 4 : (int)(sm & 15u), PASS == 2 ? (int)(cr >> 9) : 0, pst(fr, 2),
+                                PASS == 2 ? cr & 0x1ffu : 0u, false);
+            }
+            PH_RESET();
+            publish(progress, wv, mby * 65536 + mbx + 1);
+            PH_MARK(6);
         }
-        for (int i = lane; has_chain && i < mbw * 4; i += 64) a.derr[(size_t)fc * mbw * 4 + i] = tdc[i];
-        if (!PAIR) {
-            ph_flush();
-            return;
-        }
-        // frame pairs: its chain done, the wave takes luma rows (PairRowSchedule1,
-        // from the join row on); C back to the workgroup's first frame
-        C.f = f;
-        C.P = P;
-        C.T = T;
-        C.Sl = Sl;
-        C.top_u = top_u;
-        C.top_v = top_v;
-        C.top_derr = top_derr;
-        C.method = __builtin_amdgcn_readfirstlane(P->method);
     }
+}
 
-    if (PASS == 1) __builtin_amdgcn_s_setprio(ZW_LUMA_PRIO);
+// ---------------------------------------------------------------------------
+// The row-parallel window: an MB's slice of the row above's state, pulled from
+// the frame's global row arrays before the MB and pushed (the MB's own bottom
+// row and contexts, for the row below) after it.  Which lane moves which word:
+// lanes 0-3 top_y, and in pass 2 (pass 1's luma waves keep only top_y) 4-5
+// top_u, 6-7 top_v, 8-10 top_c, 11 top_derr.  op(global word, window word).
+// ---------------------------------------------------------------------------
+template <int PASS, class Op> DI void win_words(const EncWg& G, int lane, int mbx, Op op)
+{
+    WaveLds* const W = G.W;
+    if (lane < 4) op(G.gty + mbx * 16 + 4 * lane, (uint32_t*)W->win_y + lane);
+    else if (PASS == 2 && lane < 6) op(G.gtu + mbx * 8 + 4 * (lane - 4), (uint32_t*)W->win_u + (lane - 4));
+    else if (PASS == 2 && lane < 8) op(G.gtv + mbx * 8 + 4 * (lane - 6), (uint32_t*)W->win_v + (lane - 6));
+    else if (PASS == 2 && lane < 11) op(G.gtc + mbx * 12 + 4 * (lane - 8), (uint32_t*)W->win_c + (lane - 8));
+    else if (PASS == 2 && lane < 12) op(G.gtd + mbx * 4, (uint32_t*)W->win_d);
+}
+template <int PASS> DI void win_pull(const EncWg& G, int lane, int mbx)
+{
+    // (every load, then the stores: the arrays' loads are in flight together)
+    uint32_t v = 0;
+    win_words<PASS>(G, lane, mbx, [&v](const uint8_t* g, uint32_t*) { v = ld_sc1(g); });
+    win_words<PASS>(G, lane, mbx, [v](const uint8_t*, uint32_t* w) { *w = v; });
+}
+// the above-right MB's bottom row (luma only: the I4 search reads it), behind the MB's own
+DI void win_pull_right(const EncWg& G, int lane, int mbx)
+{
+    win_words<1>(G, lane, mbx + 1, [](const uint8_t* g, uint32_t* w) { w[4] = ld_sc1(g); });
+}
+template <int PASS> DI void win_push(const EncWg& G, int lane, int mbx)
+{
+    win_words<PASS>(G, lane, mbx, [](uint8_t* g, const uint32_t* w) { st_sc1(g, *w); });
+}
+
+// ---------------------------------------------------------------------------
+// The luma wavefront of the one-frame batch kernels (rows dealt to the waves by
+// RowSchedule, progress in LDS) and of the row-parallel kernels (rows by
+// ticket, progress and the row above's state in global memory).
+// ---------------------------------------------------------------------------
+template <int PASS, bool ROWS, int NW, int NCH> DI void luma_rows(const EncWg& G, Ctx& C)
+{
+    const EncArgs& a = *G.a;
+    WaveLds* const W = G.W;
+    int* const progress = G.progress;
+    const int mbw = a.mbw, mbh = a.mbh, f = G.f, lane = C.lane;
+    const int wv = __builtin_amdgcn_readfirstlane(G.wv);  // (wave-uniform: see luma_pairs)
+    const FrameLds F = frame_lds<PASS>(G, 0);
     // which wave works which row (zw_enc_rows.h)
     using RS = RowSchedule<PASS, ROWS, NW, NCH>;
     constexpr bool skip_mode = RS::skip_mode;
@@ -3471,357 +3322,37 @@ __device__ __forceinline__ void encode_body(const EncArgs& a)
         C.top_c = W->win_c;
         C.top_derr = W->win_d;
     }
-    // Everything of an MB after its searches, in three steps: the final luma
-    // transform, the final chroma transform (pass 2), and the stores.  What the
-    // transforms hand on is one word each: the blocks' has-coefficients flags
-    // (luma bits 0..15, chroma bits 0..7) and above them the simple-quant "any
-    // nonzero" flag (luma bit 16, chroma bit 8).
-    auto mb_luma = [&](Ctx& C, int lm, bool i4reuse, uint32_t i4nz, bool trel) __attribute__((always_inline)) {
-        int ynz[16];
-        uint32_t r = (uint32_t)(final_luma(C, lm, trel, ynz, i4reuse ? (int)i4nz : -1) != 0) << 16;
-#pragma unroll
-        for (int k = 0; k < 16; k++) r |= (uint32_t)(ynz[k] != 0) << k;
-        return r;
-    };
-    auto mb_chroma = [&](Ctx& C, int cm) __attribute__((always_inline)) {
-        int uvnz[8];
-        uint32_t r = (uint32_t)(final_chroma(C, cm, C.top_derr + C.od, uvnz) != 0) << 8;
-#pragma unroll
-        for (int k = 0; k < 8; k++) r |= (uint32_t)(uvnz[k] != 0) << k;
-        return r;
-    };
-    // the stores: the complexity contexts (pass 2), the levels, the MB record
-    // and the borders (the chroma borders only if the caller has not stored them)
-    auto mb_finish = [&](Ctx& C, int lm, int cm, uint32_t lres, uint32_t cres, bool chroma_borders)
-                         __attribute__((always_inline)) {
-        const int lane = C.lane;
-        int ynz[16], uvnz[8];
-#pragma unroll
-        for (int k = 0; k < 16; k++) ynz[k] = (int)((lres >> k) & 1u);
-#pragma unroll
-        for (int k = 0; k < 8; k++) uvnz[k] = (int)((cres >> k) & 1u);
-        const int lnz = (int)((lres >> 16) & 1u), cnz = (int)((cres >> 8) & 1u);
-        ZwMbOut* o = a.out + (size_t)C.f * nmb + (size_t)C.mby * mbw + C.mbx;
-        if (PASS == 2) {
-            const int skip = !(lnz | cnz);
-            // complexity (encode_residual_data semantics / skip clearing)
-            if (lane == 0) {
-                uint8_t* tc = C.top_c + C.ocx;
-                uint8_t* lc = C.M->left_c;
-                if (skip) {
-                    for (int k = 1; k < 9; k++) tc[k] = lc[k] = 0;
-                    if (lm != 4) tc[0] = lc[0] = 0;
-                } else {
-                    if (lm != 4) {
-                        int y2nz = 0;
-                        for (int n = 0; n < 16; n++) y2nz |= C.M->lev[16][n] != 0;
-                        tc[0] = lc[0] = (uint8_t)y2nz;
-                    }
-                    for (int x = 0; x < 4; x++) tc[1 + x] = (uint8_t)ynz[12 + x];
-                    for (int y = 0; y < 4; y++) lc[1 + y] = (uint8_t)ynz[y * 4 + 3];
-                    tc[5] = (uint8_t)uvnz[2];
-                    tc[6] = (uint8_t)uvnz[3];
-                    lc[5] = (uint8_t)uvnz[1];
-                    lc[6] = (uint8_t)uvnz[3];
-                    tc[7] = (uint8_t)uvnz[6];
-                    tc[8] = (uint8_t)uvnz[7];
-                    lc[7] = (uint8_t)uvnz[5];
-                    lc[8] = (uint8_t)uvnz[7];
-                }
-                o->skip = (uint8_t)skip;
-                o->chroma_mode = (uint8_t)cm;
-            }
-            if (chroma_borders) store_chroma_borders(C);
-            write_levels(C, 0, 25, skip);
-            if (a.sizes) {
-                // the packed record size k_pack_size would compute from these
-                // levels: header, eob bytes and every block's levels up to its eob
-                int e = 0;
-                if (lane < 25 && !skip) {
-                    const uint32_t* lw = (const uint32_t*)C.M->lev[lane];
-#pragma unroll
-                    for (int q = 0; q < 8; q++) {
-                        const uint32_t v = lw[q];
-                        e = (v >> 16) ? 2 * q + 2 : ((v & 0xffffu) ? 2 * q + 1 : e);
-                    }
-                }
-                // lanes 0..24 hold the eobs: DPP sums per 16-lane row, rows 0 and 1 added
-                const int r16 = red16(e);
-                const int es = __builtin_amdgcn_readlane(r16, 0) + __builtin_amdgcn_readlane(r16, 16);
-                if (lane == 0)
-                    a.sizes[(size_t)C.f * nmb + (size_t)C.mby * mbw + C.mbx] = (uint32_t)(1 + (lm == 4 ? 8 : 0) + 25 + 2 * es);
-            }
-        } else {
-            write_levels(C, 0, 17, false);
-            if (lane == 0) o->skip = 0;  // pass-1 skip is decided on the host from the levels
-        }
-        if (lane == 0) {
-            o->luma_mode = (uint8_t)lm;
-            o->segment = (uint8_t)C.seg;
-        }
-        if (lane < 16) o->bpred[lane] = lm == 4 ? C.M->modes[lane] : 0;
-        store_luma_borders(C);
-    };
-    auto mb_store = [&](Ctx& C, int lm, int cm, bool i4reuse, uint32_t i4nz, bool trel) __attribute__((always_inline)) {
-        [[maybe_unused]] const int lane = C.lane;
-        PH_START();
-        const uint32_t lres = mb_luma(C, lm, i4reuse, i4nz, trel);
-        PH_MARK(4);
-        const uint32_t cres = PASS == 2 ? mb_chroma(C, cm) : 0u;
-        PH_MARK(5);
-        mb_finish(C, lm, cm, lres, cres, true);
-    };
-    if constexpr (PAIR) {
-        // ---- frame pairs: every wave works MB row y of both frames of the
-        // workgroup (which wave takes which row: RP below; in pass 1 the chain
-        // waves arrive here after their chains and take rows from the join row
-        // on), MB (x, y) of frame 0 and of frame 1 per iteration.  Both
-        // frames' rows advance together, so one progress word per wave serves
-        // both.  The two MBs' I4 searches run in one wave (pick_i4_pair): lanes
-        // 0..31 frame 0, lanes 32..63 frame 1.  The other per-MB stages run in
-        // loops over the frames (not unrolled: one copy of their code), and what
-        // an MB's stages hand on goes through LDS (W->pst), not registers.
-        MbLds* const Mp[2] = {&W->mb, Mall2 + wv};
-        const int meth0 = C.method;
-        const int K = C.method <= 3 ? 3 : (C.method == 4 ? 4 : 10);
-        // per-frame encoder settings (a launch's frames normally share them)
-        const int meth1 = nf == 2 ? __builtin_amdgcn_readfirstlane(a.params[f + 1].method) : C.method;
-        const bool trel1 = PASS == 2 && nf == 2 && __builtin_amdgcn_readfirstlane(a.params[f + 1].do_trellis);
-        const bool keep1 = !trel1 && (PASS == 1 || a.dbg == nullptr);
-        // pass 2: the waves take the rows in turn; pass 1: fewer rows for the
-        // luma waves beside a chain, and from the join row on the chain waves'
-        // too (PairRowSchedule1)
-        using RP =
-            typename std::conditional<PASS == 1, PairRowSchedule1<NW, NCW>, RowSchedule<PASS, ROWS, NW, NCW, true>>::type;
-        const bool same_k = nf == 1 || (meth1 == C.method && trel1 == trel);
-        for (int mby = RP::first_row(wv, mbh); mby < mbh; mby = RP::next_row(wv, mby, mbh)) {
-#pragma unroll
-            for (int fr = 0; fr < 2; fr++) row_start(Mp[fr], lane);
-            wsync();
-            const int prevw = mby > 0 ? RP::wave_of_row(mby - 1, mbh) : 0;
-            auto wait_above = [&](int need) {
-                if (mby > 0) wait_row(progress, prevw, (mby - 1) * 65536 + need);
-            };
-            for (int mbx = 0; mbx < mbw; mbx++) {
-                PH_START();
-                const int lane = opaque_lane(threadIdx.x & 63);
-                C.lane = lane;
-                // point C at frame fr's MB (x, y)
-                auto enter = [&](int fr) {
-                    // a fresh opaque lane per MB stage: lane-derived constants are
-                    // recomputed, not held across the other frame's stages
-                    C.lane = opaque_lane(threadIdx.x & 63);
-                    C.f = f + fr;
-                    C.P = a.params + C.f;
-                    C.T = (const LdsTables*)((const uint8_t*)T + L.sT * fr);
-                    C.Sl = (const ZwSegment*)((const uint8_t*)Sl + L.sS * fr);
-                    C.top_y = top_y + L.sy * fr;
-                    C.top_u = top_u + L.su * fr;
-                    C.top_v = top_v + L.sv * fr;
-                    C.top_c = top_c + L.sc * fr;
-                    C.top_derr = top_derr + L.sd * fr;
-                    C.M = fr ? Mp[1] : Mp[0];
-                    C.method = fr ? meth1 : meth0;
-                    C.mbx = mbx;
-                    C.mby = mby;
-                    C.oy = mbx * 16;
-                    C.oc = mbx * 8;
-                    C.ocx = mbx * 12;
-                    C.od = mbx * 4;
-                    C.sY = C.M->sy;
-                    C.sU = C.M->su;
-                    C.sV = C.M->sv;
-                };
-                auto pst = [&](int fr, int k) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)W->pst[fr][k]); };
-                wait_above(min(mbx + 1, mbw));
-                luma_issue_prio<PASS>(progress, prevw, mbx, mby, mbw);
-                PH_MARK(0);
-ZW_PAIR_LOOP
-                for (int fr = 0; fr < 2; fr++) {
-                    if (fr >= nf) {
-                        if (lane == 0) W->pst[fr][0] = 0;  // (no frame 1: no search)
-                        continue;
-                    }
-                    enter(fr);
-                    const MbFetch fm = fetch_mb(&a, C.f, lane, mbx, mby);
-                    setup_ctx(C, &a, seg_lut + L.sL * fr, W, mbx, mby, fm);
-                    build_luma_border(C, 0);
-                    int l_;
-                    unsigned long long s_;
-                    pick_i16<PASS>(C, l_, s_);
-                    const bool n_ = C.method > 1 && (C.method >= 5 || s_ > 211ull * C.S->l_mode || l_ != 0);
-                    if (lane == 0) {
-                        W->pst[fr][0] = (uint32_t)l_ | ((uint32_t)n_ << 4) | ((uint32_t)C.seg << 8);
-                        W->pst[fr][1] = (uint32_t)s_;
-                        W->pst[fr][2] = (uint32_t)(s_ >> 32);
-                        W->pst[fr][3] = 0;
-                    }
-                    wsync();
-                }
-                wsync();
-                PH_MARK(1);
-                const uint32_t s0 = pst(0, 0), s1 = pst(1, 0);
-                const bool n0 = (s0 >> 4) & 1u, n1 = (s1 >> 4) & 1u;
-                if (n0 || n1) wait_above(min(mbx + 2, mbw));
-ZW_PAIR_LOOP
-                for (int fr = 0; fr < 2; fr++) {
-                    if (!((pst(fr, 0) >> 4) & 1u)) continue;
-                    enter(fr);
-                    build_luma_border(C, 1);
-                }
-                PH_MARK(21);
-                if (K <= 4 && same_k && (n0 || n1)) {
-                    Ctx CA = C, CB = C;
-                    CA.lane = CB.lane = opaque_lane(threadIdx.x & 63);
-                    CA.T = T;
-                    CB.T = (const LdsTables*)((const uint8_t*)T + L.sT);
-                    CA.M = Mp[0];
-                    CB.M = Mp[1];
-                    CA.S = Sl + (s0 >> 8);
-                    CB.S = (const ZwSegment*)((const uint8_t*)Sl + L.sS) + (s1 >> 8);
-                    CA.sY = Mp[0]->sy;
-                    CB.sY = Mp[1]->sy;
-                    const unsigned long long i0 = pst(0, 1) | ((unsigned long long)pst(0, 2) << 32);
-                    const unsigned long long i1 = pst(1, 1) | ((unsigned long long)pst(1, 2) << 32);
-                    uint32_t z0 = 0, z1 = 0;
-                    const uint32_t r = pick_i4_pair<PASS>(CA, CB, i0, i1, n0, n1, keep_i4, z0, z1);
-                    if (lane == 0) {
-                        W->pst[0][3] = (r & 1u) ? (z0 | 0x10000u) : 0u;
-                        W->pst[1][3] = (r & 2u) ? (z1 | 0x10000u) : 0u;
-                    }
-                } else if (n0 || n1) {
-ZW_PAIR_LOOP
-                    for (int fr = 0; fr < 2; fr++) {
-                        const uint32_t sm = pst(fr, 0);
-                        if (!((sm >> 4) & 1u)) continue;
-                        enter(fr);
-                        C.seg = (int)(sm >> 8);
-                        C.S = C.Sl + C.seg;
-                        uint32_t z = 0;
-                        const bool w4 = pick_i4<PASS>(C, pst(fr, 1) | ((unsigned long long)pst(fr, 2) << 32),
-                                                      fr ? keep1 : keep_i4, z);
-                        if (lane == 0) W->pst[fr][3] = w4 ? (z | 0x10000u) : 0u;
-                    }
-                }
-                wsync();
-                PH_MARK(2);
-                // The final stage.  Chroma first, frame by frame (pass 2; in pass 1
-                // the chain waves work it): W->uvc, cu and cv are the wave's, so a
-                // frame's final chroma and chroma borders are done before the other
-                // frame's search.  Its result replaces the I16 score in W->pst.
-                if (PASS == 2) {
-ZW_PAIR_LOOP
-                    for (int fr = 0; fr < 2; fr++) {
-                        if (fr >= nf) continue;
-                        enter(fr);
-                        C.seg = (int)(pst(fr, 0) >> 8);
-                        C.S = C.Sl + C.seg;
-                        build_chroma_border(C);
-                        const int cm = pick_uv<PASS>(C);
-                        PH_MARK(3);
-                        const uint32_t cres = mb_chroma(C, cm);
-                        store_chroma_borders(C);
-                        if (lane == 0) W->pst[fr][1] = cres | ((uint32_t)cm << 9);
-                        PH_MARK(5);
-                    }
-                }
-                // Luma: two I16 MBs in one pass of the wave (final_luma_pair),
-                // anything else (an I4 MB, the odd last workgroup, frames whose
-                // trellis settings differ) frame by frame.
-                const uint32_t w0 = pst(0, 3), w1 = pst(1, 3);
-                if (nf == 2 && !((w0 | w1) & 0x10000u) && trel == trel1) {
-                    Ctx CA = C, CB = C;
-                    CA.lane = CB.lane = opaque_lane(threadIdx.x & 63);
-                    CA.f = f;
-                    CB.f = f + 1;
-                    CA.T = T;
-                    CB.T = (const LdsTables*)((const uint8_t*)T + L.sT);
-                    CA.M = Mp[0];
-                    CB.M = Mp[1];
-                    CA.S = Sl + (s0 >> 8);
-                    CB.S = (const ZwSegment*)((const uint8_t*)Sl + L.sS) + (s1 >> 8);
-                    CA.sY = Mp[0]->sy;
-                    CB.sY = Mp[1]->sy;
-                    CA.top_y = top_y;
-                    CB.top_y = top_y + L.sy;
-                    CA.top_c = top_c;
-                    CB.top_c = top_c + L.sc;
-                    CA.mbx = CB.mbx = mbx;
-                    CA.mby = CB.mby = mby;
-                    CA.oy = CB.oy = mbx * 16;
-                    CA.ocx = CB.ocx = mbx * 12;
-                    uint32_t r0, r1;
-                    final_luma_pair(CA, CB, (int)(s0 & 15u), (int)(s1 & 15u), trel, r0, r1);
-                    if (lane == 0) {
-                        W->pst[0][2] = r0;
-                        W->pst[1][2] = r1;
-                    }
-                } else {
-ZW_PAIR_LOOP
-                    for (int fr = 0; fr < 2; fr++) {
-                        if (fr >= nf) continue;
-                        enter(fr);
-                        const uint32_t sm = pst(fr, 0), r4 = pst(fr, 3);
-                        C.seg = (int)(sm >> 8);
-                        C.S = C.Sl + C.seg;
-                        const bool w4 = (r4 >> 16) & 1u;
-                        const uint32_t lres = mb_luma(C, w4 ? 4 : (int)(sm & 15u), w4 && (fr ? keep1 : keep_i4),
-                                                      r4 & 0xffffu, fr ? trel1 : trel);
-                        if (lane == 0) W->pst[fr][2] = lres;
-                    }
-                    if (nf == 2) PH_COUNT(26);
-                }
-                wsync();
-                PH_MARK(4);
-                // the stores, frame by frame
-ZW_PAIR_LOOP
-                for (int fr = 0; fr < 2; fr++) {
-                    if (fr >= nf) continue;
-                    enter(fr);
-                    const uint32_t sm = pst(fr, 0), r4 = pst(fr, 3), cr = pst(fr, 1);
-                    C.seg = (int)(sm >> 8);
-                    C.S = C.Sl + C.seg;
-                    const bool w4 = (r4 >> 16) & 1u;
-                    mb_finish(C, w4 ? 4 : (int)(sm & 15u), PASS == 2 ? (int)(cr >> 9) : 0, pst(fr, 2),
-                              PASS == 2 ? cr & 0x1ffu : 0u, false);
-                }
-                PH_RESET();
-                publish(progress, wv, mby * 65536 + mbx + 1);
-                PH_MARK(6);
-            }
-        }
-        ph_flush();
-        return;
-    }
-    uint8_t* const gty = ROWS ? rb + RL.ty : nullptr;
-    uint8_t* const gtu = ROWS ? rb + RL.tu : nullptr;
-    uint8_t* const gtv = ROWS ? rb + RL.tv : nullptr;
-    uint8_t* const gtc = ROWS ? rb + RL.tc : nullptr;
-    uint8_t* const gtd = ROWS ? rb + RL.td : nullptr;
+    // Pass 1 loads the MB's source words and alpha at the top of its iteration,
+    // in flight during the wait for the row above; pass 2 fetches them one MB
+    // ahead.  (Fetched ahead, pass 1's words do not stay in registers: each is
+    // spilled to scratch right after its load, so the three loads run one after
+    // another, each also waiting for the previous MB's stores -- vmcnt counts
+    // stores.  Measured per 256 1080p frames: pass 1 29.12 -> 28.98 ms loading
+    // at the top, pass 2 37.38 -> 37.64 ms.)
+    constexpr bool fetch_ahead = PASS == 2;
     for (int it = 0, yk = rw;; it++) {
-        const int mby = ROWS ? row_ticket(&rsync[0]) : (skip_mode ? yk : rw + it * nrw);
+        const int mby = __builtin_amdgcn_readfirstlane(ROWS ? row_ticket(&G.rsync[0]) : (skip_mode ? yk : rw + it * nrw));
         if (skip_mode) yk = RS::next_row(wv, yk, mbh);
         if (mby >= mbh) break;
         row_start(C.M, lane);
         wsync();
         const int prevw = (!ROWS && mby > 0) ? RS::wave_of_row(mby - 1) : 0;
         int seen = -1;  // ROWS: last progress value read of the row above
-        int* const prog_above = ROWS ? rsync + 4 + (mby > 0 ? mby - 1 : 0) : nullptr;
+        int* const prog_above = ROWS ? G.rsync + 4 + (mby > 0 ? mby - 1 : 0) : nullptr;
         // the row above has finished `need` MBs
         auto wait_above = [&](int need) {
             if (mby == 0) return;
-            if (ROWS) row_wait(prog_above, need, rerr, seen);
+            if (ROWS) row_wait(prog_above, need, G.rerr, seen);
             else wait_row(progress, prevw, (mby - 1) * 65536 + need);
         };
-        // (pass 2 fetches the MB's words one MB ahead: see ZW_FETCH_AHEAD)
         MbFetch nx;
-        if (ZW_FETCH_AHEAD) nx = fetch_mb(&a, f, lane, 0, mby);
+        if (fetch_ahead) nx = fetch_mb(&a, f, lane, 0, mby);
         for (int mbx = 0; mbx < mbw; mbx++) {
             PH_START();
             const int lane = opaque_lane(threadIdx.x & 63);
             C.lane = lane;
             MbFetch cur;
-            if (ZW_FETCH_AHEAD) {
+            if (fetch_ahead) {
                 cur = nx;
                 if (mbx + 1 < mbw) nx = fetch_mb(&a, f, lane, mbx + 1, mby);
             } else {
@@ -3832,19 +3363,8 @@ ZW_PAIR_LOOP
             // (x+1, y-1) only then, so the wait overlaps the first searches
             wait_above(min(mbx + 1, mbw));
             if (ROWS) {
-                // pull this MB's slice of the row above's state into the window
                 if (mby > 0) {
-                    uint32_t v = 0;
-                    if (lane < 4) v = ld_sc1(gty + mbx * 16 + 4 * lane);
-                    else if (PASS == 2 && lane < 6) v = ld_sc1(gtu + mbx * 8 + 4 * (lane - 4));
-                    else if (PASS == 2 && lane < 8) v = ld_sc1(gtv + mbx * 8 + 4 * (lane - 6));
-                    else if (PASS == 2 && lane < 11) v = ld_sc1(gtc + mbx * 12 + 4 * (lane - 8));
-                    else if (PASS == 2 && lane < 12) v = ld_sc1(gtd + mbx * 4);
-                    if (lane < 4) ((uint32_t*)W->win_y)[lane] = v;
-                    else if (PASS == 2 && lane < 6) ((uint32_t*)W->win_u)[lane - 4] = v;
-                    else if (PASS == 2 && lane < 8) ((uint32_t*)W->win_v)[lane - 6] = v;
-                    else if (PASS == 2 && lane < 11) ((uint32_t*)W->win_c)[lane - 8] = v;
-                    else if (PASS == 2 && lane < 12) ((uint32_t*)W->win_d)[0] = v;
+                    win_pull<PASS>(G, lane, mbx);
                 } else if (PASS == 2) {
                     // row 0: zero contexts; top_derr from pass 1 (quirk A6)
                     if (lane < 3) ((uint32_t*)W->win_c)[lane] = 0;
@@ -3860,7 +3380,7 @@ ZW_PAIR_LOOP
             }
             if (!ROWS) luma_issue_prio<PASS>(progress, prevw, mbx, mby, mbw);
             PH_MARK(0);
-            setup_ctx(C, &a, seg_lut, W, mbx, mby, cur);
+            setup_ctx(C, &a, G.seg_lut, W, mbx, mby, cur);
             build_luma_border(C, 0);
             int lm;
             unsigned long long i16s;
@@ -3880,32 +3400,25 @@ ZW_PAIR_LOOP
                 if (C.method >= 5 || i16s > thr || lm != 0) {
                     wait_above(min(mbx + 2, mbw));
                     if (ROWS && mby > 0 && mbx + 1 < mbw) {
-                        // the above-right MB's bottom row
-                        uint32_t v = 0;
-                        if (lane < 4) v = ld_sc1(gty + (mbx + 1) * 16 + 4 * lane);
-                        if (lane < 4) ((uint32_t*)W->win_y)[4 + lane] = v;
+                        win_pull_right(G, lane, mbx);
                         wsync();
                     }
                     build_luma_border(C, 1);
                     PH_MARK(21);
-                    if (pick_i4<PASS>(C, i16s, keep_i4, i4nz)) {
+                    if (pick_i4<PASS>(C, i16s, F.keep_i4, i4nz)) {
                         lm = 4;
-                        i4reuse = keep_i4;
+                        i4reuse = F.keep_i4;
                     }
                 }
             }
             PH_MARK(2);
-            mb_store(C, lm, cm, i4reuse, i4nz, trel);
+            mb_store<PASS>(C, lm, cm, i4reuse, i4nz, F.trel);
             PH_RESET();
             if (ROWS) {
                 // push this MB's state for the row below (sc1), then publish
                 if (mby + 1 < mbh) {
-                    if (lane < 4) st_sc1(gty + mbx * 16 + 4 * lane, ((const uint32_t*)W->win_y)[lane]);
-                    else if (PASS == 2 && lane < 6) st_sc1(gtu + mbx * 8 + 4 * (lane - 4), ((const uint32_t*)W->win_u)[lane - 4]);
-                    else if (PASS == 2 && lane < 8) st_sc1(gtv + mbx * 8 + 4 * (lane - 6), ((const uint32_t*)W->win_v)[lane - 6]);
-                    else if (PASS == 2 && lane < 11) st_sc1(gtc + mbx * 12 + 4 * (lane - 8), ((const uint32_t*)W->win_c)[lane - 8]);
-                    else if (PASS == 2 && lane < 12) st_sc1(gtd + mbx * 4, ((const uint32_t*)W->win_d)[0]);
-                    row_publish(rsync + 4 + mby, mbx + 1);
+                    win_push<PASS>(G, lane, mbx);
+                    row_publish(G.rsync + 4 + mby, mbx + 1);
                 }
             } else {
                 publish(progress, wv, mby * 65536 + mbx + 1);
@@ -3913,7 +3426,43 @@ ZW_PAIR_LOOP
             PH_MARK(6);
         }
     }
-    ph_flush();
+}
+
+// ---------------------------------------------------------------------------
+// An encode kernel: carve the LDS, fill the shared state, build the wave's Ctx,
+// then the wave's role.
+// ---------------------------------------------------------------------------
+template <int PASS, bool ROWS, int FP = 1> DI void encode_body(const EncArgs& a)
+{
+    using SH = EncShape<PASS, ROWS, FP>;
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const int lane = threadIdx.x & 63;
+    const EncWg G = enc_carve<PASS, ROWS, FP>(a, smem);
+    // pass 1's chroma chain: workgroup 0 of each frame in the row-parallel
+    // kernels (it keeps the frame-wide top_u/v/derr in LDS), the first waves of
+    // the batch kernels
+    const bool chain_wg = PASS == 1 && (ROWS ? blockIdx.x == 0 : G.wv < SH::NCW);
+    enc_fill<PASS, ROWS, FP>(G, chain_wg);
+
+    Ctx C;
+    C.a = &a;
+    C.W = G.W;
+    C.lane = lane;
+    ctx_enter(C, frame_lds<PASS>(G, 0), &G.W->mb, 0, 0);
+    ph_init(G, lane);
+
+    if (chain_wg) {
+        __builtin_amdgcn_s_setprio(ZW_CHAIN_PRIO);  // (issue priority: see ZW_CHAIN_PRIO)
+        if constexpr (SH::NCH == 2 && !SH::PAIR) chain_quad<PASS>(G, C);
+        else chain_one<PASS, FP>(G, C);
+    }
+    // (in frame pairs the chain waves, their chains done, take luma rows)
+    if (!chain_wg || SH::PAIR) {
+        if (PASS == 1) __builtin_amdgcn_s_setprio(ZW_LUMA_PRIO);
+        if constexpr (SH::PAIR) luma_pairs<PASS, SH::NW, SH::NCW>(G, C);
+        else luma_rows<PASS, ROWS, SH::NW, SH::NCH>(G, C);
+    }
+    ph_flush<PASS>(G, lane);
 }
 
 extern "C" __global__ __launch_bounds__(PassShape<1>::WG) void k_encode_pass1(EncArgs a) { encode_body<1, false>(a); }
@@ -3922,108 +3471,6 @@ extern "C" __global__ __launch_bounds__(PassShape<2>::WG) void k_encode_pass2(En
 extern "C" __global__ __launch_bounds__(PassShape<2>::WG) void k_encode_pass2_fp(EncArgs a) { encode_body<2, false, 2>(a); }
 extern "C" __global__ __launch_bounds__(64 * RowsShape<1>::NW) void k_encode_rows_pass1(EncArgs a) { encode_body<1, true>(a); }
 extern "C" __global__ __launch_bounds__(64) void k_encode_rows_pass2(EncArgs a) { encode_body<2, true>(a); }
-
-// ---------------------------------------------------------------------------
-// Kernel-level entry: quantisation (simple or trellis) of independent 4x4
-// coefficient blocks, one block per thread (quantize_coeff cost.rs:457,
-// trellis_quantize_block cost.rs:788).  Used by the parity tests and as the
-// building block the encoder kernels share.
-// ---------------------------------------------------------------------------
-struct QuantBlocksArgs {
-    ZwMatrix m;
-    uint16_t sharpen[16];
-    uint32_t lambda;
-    int32_t ctype, first, trel, n;
-};
-
-extern "C" __global__ __launch_bounds__(256) void k_quant_blocks(const int* __restrict__ coeffs,
-                                                                const uint8_t* __restrict__ ctx0s,
-                                                                const ZwLevelCosts* __restrict__ lcost,
-                                                                const uint8_t* __restrict__ probs, QuantBlocksArgs a,
-                                                                int* __restrict__ levels, int* __restrict__ dq)
-{
-    __shared__ LdsTables T;
-    for (int i = threadIdx.x; i < (int)(sizeof(T.lc) / 2); i += 256) (&T.lc[0][0][0][0])[i] = (&lcost->lc[0][0][0][0])[i];
-    for (int i = threadIdx.x; i < 96; i += 256) {
-        (&T.eob[0][0][0])[i] = (&lcost->eob[0][0][0])[i];
-        (&T.init[0][0][0])[i] = (&lcost->init[0][0][0])[i];
-    }
-    for (int i = threadIdx.x; i < 4 * 8 * 3 * 11; i += 256) (&T.probs[0][0][0][0])[i] = probs[i];
-    load_static_tables(&T, threadIdx.x, 256, probs);
-    __syncthreads();
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= a.n) return;
-    int c[16], lv[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) c[k] = coeffs[(size_t)b * 16 + k];
-    const int ctx0 = ctx0s[b];
-    if (a.trel) {
-        if (a.first) trellis<1>(c, lv, a.m, a.sharpen, a.lambda, &T, a.ctype, ctx0);
-        else trellis<0>(c, lv, a.m, a.sharpen, a.lambda, &T, a.ctype, ctx0);
-        if (a.first) lv[0] = 0;
-    } else {
-#pragma unroll
-        for (int n = 0; n < 16; n++) {
-            const int j = kZZ(n);
-            lv[n] = n < a.first ? 0 : quantz(c[j], a.m.iq[j > 0], a.m.bias[j > 0]);
-        }
-#pragma unroll
-        for (int n = 0; n < 16; n++) {
-            const int j = kZZ(n);
-            c[j] = n < a.first ? 0 : m24(lv[n], (int)a.m.q[j > 0]);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        levels[(size_t)b * 16 + k] = lv[k];
-        dq[(size_t)b * 16 + k] = c[k];
-    }
-}
-
-// The lane-parallel trellis (trellis_g, used by the final I4 pass): 16 lanes
-// per block, lane = zigzag position.
-extern "C" __global__ __launch_bounds__(256) void k_quant_blocks_g(const int* __restrict__ coeffs,
-                                                                  const uint8_t* __restrict__ ctx0s,
-                                                                  const ZwLevelCosts* __restrict__ lcost,
-                                                                  const uint8_t* __restrict__ probs, QuantBlocksArgs a,
-                                                                  int* __restrict__ levels, int* __restrict__ dq)
-{
-    __shared__ LdsTables T;
-    for (int i = threadIdx.x; i < (int)(sizeof(T.lc) / 2); i += 256) (&T.lc[0][0][0][0])[i] = (&lcost->lc[0][0][0][0])[i];
-    for (int i = threadIdx.x; i < 96; i += 256) {
-        (&T.eob[0][0][0])[i] = (&lcost->eob[0][0][0])[i];
-        (&T.init[0][0][0])[i] = (&lcost->init[0][0][0])[i];
-    }
-    for (int i = threadIdx.x; i < 4 * 8 * 3 * 11; i += 256) (&T.probs[0][0][0][0])[i] = probs[i];
-    load_static_tables(&T, threadIdx.x, 256, probs);
-    __syncthreads();
-    const int b = (int)((blockIdx.x * 256 + threadIdx.x) >> 4), n = threadIdx.x & 15;
-    const int bb = min(b, a.n - 1);  // whole groups stay active (DPP/ballot need every lane)
-    const int cn = coeffs[(size_t)bb * 16 + zz_of(n)];
-    const int ctx0 = ctx0s[bb];
-    int lvl;
-    if (a.first) (void)trellis_g<1>(cn, n, a.m, a.sharpen, a.lambda, &T, a.ctype, ctx0, lvl);
-    else (void)trellis_g<0>(cn, n, a.m, a.sharpen, a.lambda, &T, a.ctype, ctx0, lvl);
-    if (b < a.n) {
-        const int j = zz_of(n);
-        levels[(size_t)b * 16 + n] = lvl;
-        // positions before `first` keep their input coefficient (as trellis<1> leaves coeffs[0])
-        dq[(size_t)b * 16 + j] = n < a.first ? cn : lvl * (int)(j == 0 ? a.m.q[0] : a.m.q[1]);
-    }
-}
-
-extern "C" hipError_t zwk_quant_blocks(hipStream_t s, const int* coeffs, const uint8_t* ctx0s, const ZwLevelCosts* lcost,
-                                       const uint8_t* probs, const void* args, int* levels, int* dq)
-{
-    const QuantBlocksArgs& a = *(const QuantBlocksArgs*)args;
-    if (a.trel == 2)
-        hipLaunchKernelGGL(k_quant_blocks_g, dim3((a.n * 16 + 255) / 256), dim3(256), 0, s, coeffs, ctx0s, lcost, probs,
-                           a, levels, dq);
-    else
-        hipLaunchKernelGGL(k_quant_blocks, dim3((a.n + 255) / 256), dim3(256), 0, s, coeffs, ctx0s, lcost, probs, a,
-                           levels, dq);
-    return hipGetLastError();
-}
 
 static size_t encode_lds_bytes(int mbw, int nw, bool rows, int pass, int fp = 1)
 {
@@ -4051,49 +3498,6 @@ static bool encode_fp_for(int pass, int mbw, int nframes)
     return mode == 1 || nframes >= 2 * cus;
 }
 extern "C" int zwk_encode_fp(int pass, int mbw, int nframes) { return encode_fp_for(pass, mbw, nframes) ? 1 : 0; }
-
-
-// ---------------------------------------------------------------------------
-// Host-side launch wrappers (called from zw_host.cpp).
-// ---------------------------------------------------------------------------
-extern "C" hipError_t zwk_rgb2yuv(hipStream_t s, const uint8_t* img, int w, int h, int bpp, int mbw, int mbh,
-                                  uint8_t* Y, uint8_t* U, uint8_t* V, size_t img_stride, size_t ysz, size_t csz,
-                                  int nframes)
-{
-    // the row-coalesced kernel needs every 8-pixel run aligned for its loads
-    // (16 B for RGBA, 8 B for RGB) and 8-byte aligned luma rows
-    const uintptr_t base = (uintptr_t)img;
-    const bool planes_ok = ((uintptr_t)Y | (uintptr_t)U | (uintptr_t)V | ysz | csz) % 8 == 0;
-    const int ng = mbw * 2 * mbh * 8;
-    if (planes_ok && bpp == 4 && base % 16 == 0 && img_stride % 16 == 0 && w % 4 == 0) {
-        hipLaunchKernelGGL(k_rgb2yuv_rows<4>, dim3((ng + 255) / 256, nframes), dim3(256), 0, s, img, w, h, mbw, mbh,
-                           Y, U, V, img_stride, ysz, csz);
-    } else if (planes_ok && bpp == 3 && base % 8 == 0 && img_stride % 8 == 0 && w % 8 == 0) {
-        hipLaunchKernelGGL(k_rgb2yuv_rows<3>, dim3((ng + 255) / 256, nframes), dim3(256), 0, s, img, w, h, mbw, mbh,
-                           Y, U, V, img_stride, ysz, csz);
-    } else {
-        const int n = mbw * 8 * mbh * 8;
-        hipLaunchKernelGGL(k_rgb2yuv, dim3((n + 255) / 256, nframes), dim3(256), 0, s, img, w, h, bpp, mbw, mbh, Y, U,
-                           V, img_stride, ysz, csz);
-    }
-    return hipGetLastError();
-}
-
-extern "C" hipError_t zwk_analysis(hipStream_t s, const uint8_t* Y, const uint8_t* U, const uint8_t* V, int mbw,
-                                   int mbh, size_t ysz, size_t csz, uint8_t* alpha, uint32_t* histo, int nframes)
-{
-    const int nmb = mbw * mbh;
-    hipLaunchKernelGGL(k_analysis4, dim3((nmb + 16 * ZW_AN4_GPW - 1) / (16 * ZW_AN4_GPW), nframes), dim3(256), 0, s, Y, U,
-                       V, mbw, mbh, ysz, csz, alpha, histo);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t zwk_segments(hipStream_t s, uint32_t* histo, const ZwFrameParams* tmpl,
-                                   ZwFrameParams* params, int nframes)
-{
-    hipLaunchKernelGGL(k_segments, dim3((nframes + 63) / 64), dim3(64), 0, s, histo, tmpl, params, nframes);
-    return hipGetLastError();
-}
 
 // The widest frame (in MBs) whose LDS fits the 160 KiB of a CU in the batch
 // shapes (rows = false: every row array of the frame in LDS) or in the

@@ -7,7 +7,7 @@
 //
 // The planes equal k_rgb2yuv's of the packed u8 image the rule makes on the
 // host; that image is never materialised.  Shaped like k_rgb2yuv_rows
-// (zw_enc_kernels.hip): one thread per 8x2 luma pixels (4 chroma samples), a
+// (zw_prepass_kernels.hip): one thread per 8x2 luma pixels (4 chroma samples), a
 // wave reading 64 consecutive 8-pixel runs of two rows, 8-byte luma and 4-byte
 // chroma stores.  Loads per row of a run (nontemporal: the tensor is read once):
 //   CHW u8   one 8-byte load a plane        HWC u8 x 3   three 8-byte loads
