@@ -119,3 +119,9 @@ struct ZwY2rDev {
     size_t frame_stride, plane_stride, row_stride;
     float scale[4], bias[4];
 };
+
+// k_yuv2rgb_resize's per-frame table entry (zw_vp8_decode_batch_device_resized):
+// the frame's slot in the caller's batch and its source window in frame pixels.
+struct ZwResizeFrame {
+    uint32_t slot, cx, cy, cw, ch, pad[3];
+};

@@ -33,6 +33,9 @@ hipError_t zwk_yuv2rgb(hipStream_t s, const uint8_t* Y, const uint8_t* U, const 
 hipError_t zwk_yuv2rgb_dev(hipStream_t s, const uint8_t* Y, const uint8_t* U, const uint8_t* V, size_t ysz, size_t csz,
                            int w, int h, int ys, int cs, int layout, int dtype, int channels, int fancy, void* out,
                            const ZwY2rDev* P, int nframes);
+hipError_t zwk_yuv2rgb_resize(hipStream_t s, const uint8_t* Y, const uint8_t* U, const uint8_t* V, size_t ysz,
+                              size_t csz, int w, int h, int ys, int cs, int layout, int dtype, int channels, int fancy,
+                              void* out, const ZwY2rDev* P, const ZwResizeFrame* tab, int ow, int oh, int nframes);
 hipError_t zwk_dec_rows(hipStream_t s, int phase, const uint8_t* recs, const uint32_t* moff, const uint64_t* fbase,
                         const void* quant, uint8_t* Y, uint8_t* U, uint8_t* V, uint8_t* flags, const ZwFilterParams* fp,
                         int mbw, int mbh, size_t ysz, size_t csz, int nframes, int* rowsync, uint8_t* borders, int rows);
@@ -649,7 +652,7 @@ static int dec_tok_split(zw_ctx* ctx, const DecKnobs& K, int n, size_t nmb)
     if (K.tokens == DecKnobs::TOK_MIXED) return std::max(0, std::min(n, (int)(n * K.tokens_host) / C * C));  // whole host chunks
     // auto.  Defaults until measured: 0.19 ms of chunk time per 1080p frame (16 host
     // threads) and a 100 ms device parse for 1080p frames
-    const double host_f = ctx->dec_host_ms_per_frame > 0 ? ctx->dec_host_ms_per_frame : 0.19 * (double)nmb / 8160.0;
+    const double host_f = (ctx->dec_host_ms_per_mb > 0 ? ctx->dec_host_ms_per_mb : 0.19 / 8160.0) * (double)nmb;
     const double tok = (ctx->dec_tok_ms_per_mb > 0 ? ctx->dec_tok_ms_per_mb : 100.0 / 8160.0) * (double)nmb;
     const double tail = 0.06 * tok;  // the device frames' reconstruction and download after the parse, per frame of
                                      // host work that the parse's length leaves (an estimate; errs toward the host)
@@ -818,6 +821,7 @@ struct DecRun {
     DecChunk B[2];
     double host_parse_ms = 0;
     int host_frames = 0;
+    size_t nmb = 0;  // MBs of a frame (from the first frame's dimensions; 0: not known)
 
     DecRun(zw_ctx* c, int frames, const uint8_t* const* d, const size_t* l, DecSink& s)
         : ctx(c), n(frames), data(d), lens(l), sink(s)
@@ -833,7 +837,7 @@ struct DecRun {
     {
         const double t0 = dec_now_ms();
         int w = 0, h = 0;  // (the first frame's dimensions; dec_tok_prepare checks every frame)
-        const size_t nmb = n > 0 && peek_dims(data[0], lens[0], &w, &h) ? (size_t)((w + 15) / 16) * (size_t)((h + 15) / 16) : 0;
+        nmb = n > 0 && peek_dims(data[0], lens[0], &w, &h) ? (size_t)((w + 15) / 16) * (size_t)((h + 15) / 16) : 0;
         const int h0 = nmb ? dec_tok_split(ctx, K, n, nmb) : n;
         if (h0 >= n || !dec_tok_prepare(ctx, n, data, lens, h0, T)) T.h0 = n;
         ctx->dec_host_ms[0] += dec_now_ms() - t0;
@@ -920,7 +924,8 @@ struct DecRun {
             }
         }
         // (a chunk's parse runs while the previous chunk downloads: the chunk time is its share of the pipe)
-        if (!err && host_frames >= K.chunk && host_parse_ms > 0) ctx->dec_host_ms_per_frame = host_parse_ms / host_frames;
+        if (!err && host_frames >= K.chunk && host_parse_ms > 0 && nmb)
+            ctx->dec_host_ms_per_mb = host_parse_ms / host_frames / (double)nmb;
     }
 
     int run()
@@ -1230,33 +1235,21 @@ static bool madd(size_t a, size_t b, size_t c, size_t* out)
     return !__builtin_mul_overflow(b, c, &t) && !__builtin_add_overflow(a, t, out);
 }
 
-}  // namespace
-
-extern "C" int zw_vp8_decode_batch_device(zw_ctx* ctx, int n, const uint8_t* const* data, const size_t* lens,
-                                          const zw_device_images* out, uint32_t* width, uint32_t* height)
+// The device entries' checks of a zw_device_images, both made before anything
+// is queued.  Its layout, dtype, channels and upsampling:
+static bool device_format_ok(const zw_device_images* out)
 {
-    if (!ctx || n <= 0 || !data || !lens || !out || !out->data) return ZW_EINVAL;
-    if ((out->layout != ZW_LAYOUT_HWC && out->layout != ZW_LAYOUT_CHW) ||
-        (out->dtype != ZW_DTYPE_U8 && out->dtype != ZW_DTYPE_F16 && out->dtype != ZW_DTYPE_F32) ||
-        (out->channels != 3 && out->channels != 4) ||
-        (out->upsampling != ZW_UPSAMPLE_BILINEAR && out->upsampling != ZW_UPSAMPLE_SIMPLE))
-        return ZW_EINVAL;
-    for (int i = 0; i < n; i++)
-        if (!data[i] && lens[i]) return ZW_EINVAL;
-    DeviceSink sink;
-    {  // dimensions first (they bound what the kernel addresses)
-        DecFrame f0;
-        const int r = parse_header(f0, data[0], lens[0]);
-        if (r) return r;
-        sink.w = f0.width;
-        sink.h = f0.height;
-    }
-    const size_t w = sink.w, h = sink.h, ch = (size_t)out->channels, N = (size_t)n;
-    if (w == 0 || h == 0) return ZW_EINVALID_DIMENSIONS;
-    for (int i = 1; i < n; i++) {  // one size per batch (a frame too short for dimensions reports its own error)
-        int wi = 0, hi = 0;
-        if (peek_dims(data[i], lens[i], &wi, &hi) && ((size_t)wi != w || (size_t)hi != h)) return ZW_EINVAL;
-    }
+    return (out->layout == ZW_LAYOUT_HWC || out->layout == ZW_LAYOUT_CHW) &&
+           (out->dtype == ZW_DTYPE_U8 || out->dtype == ZW_DTYPE_F16 || out->dtype == ZW_DTYPE_F32) &&
+           (out->channels == 3 || out->channels == 4) &&
+           (out->upsampling == ZW_UPSAMPLE_BILINEAR || out->upsampling == ZW_UPSAMPLE_SIMPLE);
+}
+// ... and that n frames of w x h fit it: the stride bounds, no overlapping
+// frames, capacity >= the last addressed element + 1, `data` aligned to its
+// element and device memory on the context's device.  *elsize = the element's bytes.
+static int check_device_extent(zw_ctx* ctx, const zw_device_images* out, size_t N, size_t w, size_t h, size_t* elsize)
+{
+    const size_t ch = (size_t)out->channels;
     // the elements one frame spans, then the last element the batch addresses
     const bool chw = out->layout == ZW_LAYOUT_CHW;
     size_t span = 0, last = 0;
@@ -1269,36 +1262,194 @@ extern "C" int zw_vp8_decode_batch_device(zw_ctx* ctx, int n, const uint8_t* con
         size_t row = 0;
         if (!madd(0, w, ch, &row) || out->row_stride < row || !madd(row, h - 1, out->row_stride, &span)) return ZW_EINVAL;
     }
-    if (n > 1 && out->frame_stride < span) return ZW_EINVAL;  // frames must not overlap
+    if (N > 1 && out->frame_stride < span) return ZW_EINVAL;  // frames must not overlap
     if (!madd(span, N - 1, out->frame_stride, &last) || out->capacity < last) return ZW_EINVAL;
-    sink.elsize = out->dtype == ZW_DTYPE_U8 ? 1 : (out->dtype == ZW_DTYPE_F16 ? 2 : 4);
-    {  // device memory on the context's device, whole elements
-        size_t bytes = 0;
-        if (!madd(0, out->capacity, sink.elsize, &bytes) || ((uintptr_t)out->data & (sink.elsize - 1))) return ZW_EINVAL;
-        HIPOK(hipSetDevice(ctx->device));
-        hipPointerAttribute_t at;
-        memset(&at, 0, sizeof at);
-        if (hipPointerGetAttributes(&at, out->data) != hipSuccess) {
-            (void)hipGetLastError();  // (an unregistered host pointer)
-            return ZW_EINVAL;
-        }
-        if (at.type != hipMemoryTypeDevice || at.device != ctx->device) return ZW_EINVAL;
+    *elsize = out->dtype == ZW_DTYPE_U8 ? 1 : (out->dtype == ZW_DTYPE_F16 ? 2 : 4);
+    // device memory on the context's device, whole elements
+    size_t bytes = 0;
+    if (!madd(0, out->capacity, *elsize, &bytes) || ((uintptr_t)out->data & (*elsize - 1))) return ZW_EINVAL;
+    HIPOK(hipSetDevice(ctx->device));
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof at);
+    if (hipPointerGetAttributes(&at, out->data) != hipSuccess) {
+        (void)hipGetLastError();  // (an unregistered host pointer)
+        return ZW_EINVAL;
     }
+    if (at.type != hipMemoryTypeDevice || at.device != ctx->device) return ZW_EINVAL;
+    return ZW_OK;
+}
+
+// The caller's strides, scale and bias as the conversion kernels take them.
+static ZwY2rDev device_strides(const zw_device_images* out)
+{
+    ZwY2rDev P = {};
+    P.frame_stride = out->frame_stride;
+    P.plane_stride = out->plane_stride;
+    P.row_stride = out->row_stride;
+    for (int c = 0; c < 4; c++) {
+        P.scale[c] = out->scale[c];
+        P.bias[c] = out->bias[c];
+    }
+    return P;
+}
+
+}  // namespace
+
+extern "C" int zw_vp8_decode_batch_device(zw_ctx* ctx, int n, const uint8_t* const* data, const size_t* lens,
+                                          const zw_device_images* out, uint32_t* width, uint32_t* height)
+{
+    if (!ctx || n <= 0 || !data || !lens || !out || !out->data) return ZW_EINVAL;
+    if (!device_format_ok(out)) return ZW_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (!data[i] && lens[i]) return ZW_EINVAL;
+    DeviceSink sink;
+    {  // dimensions first (they bound what the kernel addresses)
+        DecFrame f0;
+        const int r = parse_header(f0, data[0], lens[0]);
+        if (r) return r;
+        sink.w = f0.width;
+        sink.h = f0.height;
+    }
+    const size_t w = sink.w, h = sink.h;
+    if (w == 0 || h == 0) return ZW_EINVALID_DIMENSIONS;
+    for (int i = 1; i < n; i++) {  // one size per batch (a frame too short for dimensions reports its own error)
+        int wi = 0, hi = 0;
+        if (peek_dims(data[i], lens[i], &wi, &hi) && ((size_t)wi != w || (size_t)hi != h)) return ZW_EINVAL;
+    }
+    if (int r = check_device_extent(ctx, out, (size_t)n, w, h, &sink.elsize)) return r;
     sink.layout = out->layout;
     sink.dtype = out->dtype;
     sink.channels = out->channels;
     sink.fancy = out->upsampling == ZW_UPSAMPLE_BILINEAR;
     sink.data = (uint8_t*)out->data;
-    sink.P.frame_stride = out->frame_stride;
-    sink.P.plane_stride = out->plane_stride;
-    sink.P.row_stride = out->row_stride;
-    for (int c = 0; c < 4; c++) {
-        sink.P.scale[c] = out->scale[c];
-        sink.P.bias[c] = out->bias[c];
-    }
+    sink.P = device_strides(out);
     if (int r = DecRun(ctx, n, data, lens, sink).run()) return r;
     if (width) *width = (uint32_t)w;
     if (height) *height = (uint32_t)h;
+    return ZW_OK;
+}
+
+namespace {
+
+// zw_vp8_decode_batch_device_resized's output for one group of frames of one
+// size: k_yuv2rgb_resize after the filter, from the planes into the frames'
+// slots of the caller's batch.  tab[i] = the group's frame i (its slot in the
+// batch and its window); a chunk's entries are uploaded in stream order into
+// the chunk's own scratch (lay.extra), which lives until the chunk has finished.
+struct ResizeSink : DecSink {
+    size_t w = 0, h = 0;  // the group's frame size
+    int out_w = 0, out_h = 0;
+    int layout = 0, dtype = 0, channels = 0, fancy = 0;
+    uint8_t* data = nullptr;
+    ZwY2rDev P = {};
+    std::vector<ZwResizeFrame> tab;
+    size_t extra_per_frame() const override { return sizeof(ZwResizeFrame); }
+    int enqueue(zw_ctx* ctx, DecChunk& C) override
+    {
+        const DecMeta& M = C.meta;
+        for (int i = 0; i < M.n; i++)  // (the windows were checked against these dimensions)
+            if ((size_t)M.F[i].width != w || (size_t)M.F[i].height != h) return ZW_EINVAL;
+        hipStream_t s = ctx_stream(ctx);
+        ZwResizeFrame* d_tab = (ZwResizeFrame*)(C.d + C.lay.extra);
+        HIPOK(hipMemcpyAsync(d_tab, tab.data() + C.first, (size_t)M.n * sizeof(ZwResizeFrame), hipMemcpyHostToDevice, s));
+        HIPOK(zwk_yuv2rgb_resize(s, C.d + C.lay.y, C.d + C.lay.u, C.d + C.lay.v, M.ysz, M.csz, (int)w, (int)h,
+                                 M.mbw * 16, M.mbw * 8, layout, dtype, channels, fancy, data, &P, d_tab, out_w, out_h,
+                                 M.n));
+        HIPOK(hipEventRecord(C.set->ev[DEC_EV_CALLER], s));
+        return ZW_OK;
+    }
+    DecEv wait_event() const override { return DEC_EV_CALLER; }
+    size_t staging_per_frame(const DecChunk&) const override { return 0; }
+    int copy_down(zw_ctx*, const DecChunk&, uint8_t*, int, int) override { return ZW_OK; }
+    bool place(const DecChunk&, const uint8_t*, int) override { return true; }
+};
+
+}  // namespace
+
+extern "C" int zw_vp8_decode_batch_device_resized(zw_ctx* ctx, int n, const uint8_t* const* data, const size_t* lens,
+                                                  const zw_device_images* out, uint32_t out_w, uint32_t out_h,
+                                                  const zw_rect* windows, uint32_t* widths, uint32_t* heights)
+{
+    if (!ctx || n <= 0 || !data || !lens || !out || !out->data) return ZW_EINVAL;
+    if (out_w == 0 || out_h == 0 || out_w > (1u << 20) || out_h > (1u << 20)) return ZW_EINVAL;
+    if (!device_format_ok(out)) return ZW_EINVAL;
+    for (int i = 0; i < n; i++)
+        if (!data[i] && lens[i]) return ZW_EINVAL;
+    size_t elsize = 0;
+    if (int r = check_device_extent(ctx, out, (size_t)n, out_w, out_h, &elsize)) return r;
+    // The frames' sizes and windows, and the groups: the indices of each size
+    // in frame order, the sizes in order of first appearance.  A frame whose
+    // header gives no usable size stands alone; its decode reports its error.
+    const uint32_t NO_DIMS = 0xffffffffu;
+    std::vector<uint32_t> key(n);
+    std::vector<ZwResizeFrame> win(n);
+    for (int i = 0; i < n; i++) {
+        int w = 0, h = 0;
+        const bool dims = peek_dims(data[i], lens[i], &w, &h) && w > 0 && h > 0;
+        key[i] = dims ? (uint32_t)w | ((uint32_t)h << 16) : NO_DIMS;
+        const zw_rect r = windows ? windows[i] : zw_rect{0, 0, (uint32_t)w, (uint32_t)h};
+        if (windows && (r.w == 0 || r.h == 0)) return ZW_EINVAL;
+        if (dims && ((uint64_t)r.x + r.w > (uint64_t)w || (uint64_t)r.y + r.h > (uint64_t)h)) return ZW_EINVAL;
+        win[i] = ZwResizeFrame{(uint32_t)i, r.x, r.y, r.w, r.h, {0, 0, 0}};
+    }
+    std::vector<std::vector<int>> groups;
+    {
+        std::unordered_map<uint32_t, size_t> at;
+        for (int i = 0; i < n; i++) {
+            auto it = key[i] == NO_DIMS ? at.end() : at.find(key[i]);
+            if (it == at.end()) {
+                if (key[i] != NO_DIMS) at[key[i]] = groups.size();
+                groups.emplace_back(1, i);
+            } else {
+                groups[it->second].push_back(i);
+            }
+        }
+    }
+    // One decode pass (DecRun) per group; the batch's times are the groups' sums.
+    float dec_ms[3] = {0.f, 0.f, 0.f}, tok_ms = 0.f, tok_stage_ms[3] = {0.f, 0.f, 0.f};
+    double host_ms[3] = {0, 0, 0};
+    int err = ZW_OK;
+    for (size_t g = 0; g < groups.size() && !err; g++) {
+        const std::vector<int>& idx = groups[g];
+        const uint32_t k = key[idx[0]];
+        ResizeSink sink;
+        sink.w = k == NO_DIMS ? 0 : (k & 0xffffu);
+        sink.h = k == NO_DIMS ? 0 : (k >> 16);
+        sink.out_w = (int)out_w;
+        sink.out_h = (int)out_h;
+        sink.layout = out->layout;
+        sink.dtype = out->dtype;
+        sink.channels = out->channels;
+        sink.fancy = out->upsampling == ZW_UPSAMPLE_BILINEAR;
+        sink.data = (uint8_t*)out->data;
+        sink.P = device_strides(out);
+        std::vector<const uint8_t*> gdata(idx.size());
+        std::vector<size_t> glens(idx.size());
+        sink.tab.resize(idx.size());
+        for (size_t j = 0; j < idx.size(); j++) {
+            gdata[j] = data[idx[j]];
+            glens[j] = lens[idx[j]];
+            sink.tab[j] = win[idx[j]];
+        }
+        err = DecRun(ctx, (int)idx.size(), gdata.data(), glens.data(), sink).run();
+        for (int t = 0; t < 3; t++) {
+            dec_ms[t] += ctx->dec_ms[t];
+            tok_stage_ms[t] += ctx->dec_tok_stage_ms[t];
+            host_ms[t] += ctx->dec_host_ms[t];
+        }
+        tok_ms += ctx->dec_tok_ms;
+    }
+    for (int t = 0; t < 3; t++) {
+        ctx->dec_ms[t] = dec_ms[t];
+        ctx->dec_tok_stage_ms[t] = tok_stage_ms[t];
+        ctx->dec_host_ms[t] = host_ms[t];
+    }
+    ctx->dec_tok_ms = tok_ms;
+    if (err) return err;
+    for (int i = 0; i < n; i++) {
+        if (widths) widths[i] = key[i] & 0xffffu;
+        if (heights) heights[i] = key[i] >> 16;
+    }
     return ZW_OK;
 }
 

@@ -5,7 +5,8 @@
 //   one packed record per macroblock.  The boolean decoder follows
 //   decoder/bit_reader.rs (libwebp-style 56-bit refill, one zero byte past the
 //   end then eof).  Then the CPU replay of the device token parse
-//   (zw_dbg_tokl_frame) and the WebP container parser (zw_webp_parse).
+//   (zw_dbg_tokl_frame), the resampling rule's host hook (zw_dbg_resize_taps)
+//   and the WebP container parser (zw_webp_parse).
 #include "zw_dec_parse.h"
 
 #include <cstring>
@@ -14,6 +15,7 @@
 #include "../../include/zwebp.h"
 #include "zw_vp8_tables.h"
 #include "zw_tokl.h"
+#include "zw_resize.h"
 
 using namespace zwh;
 
@@ -469,6 +471,17 @@ static uint32_t host_tok2_mb(HostTok2Mem& m, const uint8_t* modes, const uint32_
     return L.hb - hb;
 }
 }  // namespace
+
+// zw_resize.h's tap function on the host (the one k_yuv2rgb_resize runs per pixel).
+extern "C" int zw_dbg_resize_taps(uint32_t src, uint32_t dst, uint32_t o, int32_t out[3])
+{
+    if (!out || src == 0 || dst == 0 || o >= dst || src > (1u << 23)) return ZW_EINVAL;
+    const ZwTap t = zw_resize_tap(src, dst, o);
+    out[0] = t.i0;
+    out[1] = t.i1;
+    out[2] = t.f;
+    return ZW_OK;
+}
 
 extern "C" int zw_dbg_tokl_frame(const uint8_t* vp8, size_t len, int* match)
 {

@@ -129,10 +129,12 @@ struct zw_ctx {
     float dec_ms[3] = {0.f, 0.f, 0.f};
     float dec_tok_ms = 0.f;  // the device token parse of the last batch (0: the host parsed every frame)
     float dec_tok_stage_ms[3] = {0.f, 0.f, 0.f};  // its stage 1, count pass + offsets (+ the host's wait), record pass
-    // measured rates for the host / device split of the token parse (dec_tok_split):
-    // host chunk parse ms per frame (the whole chunk over all threads), device launch ms
-    // per MB of a frame (the launch runs its frames side by side), 0 = not measured yet
-    double dec_host_ms_per_frame = 0, dec_tok_ms_per_mb = 0;
+    // measured rates for the host / device split of the token parse (dec_tok_split),
+    // both per MB of a frame so that they carry over to a batch of another frame size
+    // (a mixed-size batch decodes one size after another): host chunk parse ms per
+    // frame (the whole chunk over all threads), device launch ms (the launch runs
+    // its frames side by side), 0 = not measured yet
+    double dec_host_ms_per_mb = 0, dec_tok_ms_per_mb = 0;
     // host stages of the last decode batch, wall ms summed over its chunks:
     // [0] parse (bool decoder + records), [1] download, [2] fan-out / copy-out
     double dec_host_ms[3] = {0, 0, 0};

@@ -37,6 +37,8 @@ __all__ = [
     "UpsamplingMethod", "WebPDecoder", "decode_rgb", "decode_rgba", "vp8_decode_rgb", "decode_rgb_batch",
     "decode_rgb_batch_into", "decode_rgba_into", "decode_rgb_into",
     "decode_batch_device", "decode_batch_device_ptr", "decode_webp_batch_device",
+    "decode_batch_device_resized", "decode_batch_device_resized_ptr", "decode_webp_batch_device_resized",
+    "vp8_frame_dims",
     "encode_batch_device", "encode_batch_device_ptr", "encode_webp_batch_device",
     "yuv_to_rgb", "webp_parse", "encode_frame_lossless", "encode_alpha",
 ]
@@ -121,6 +123,10 @@ class _DeviceImages(ctypes.Structure):
                 ("row_stride", ctypes.c_size_t), ("scale", ctypes.c_float * 4), ("bias", ctypes.c_float * 4)]
 
 
+class _Rect(ctypes.Structure):
+    _fields_ = [("x", ctypes.c_uint32), ("y", ctypes.c_uint32), ("w", ctypes.c_uint32), ("h", ctypes.c_uint32)]
+
+
 # (name, restype, argtypes) for every symbol in include/zwebp.h
 _VP, _SZ, _U32, _I, _U8 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint8
 SIGNATURES = [
@@ -150,6 +156,10 @@ SIGNATURES = [
                                           ctypes.POINTER(_VP), ctypes.POINTER(_SZ), _U32, _VP, _VP]),
     ("zw_vp8_decode_batch_device", _I, [_VP, _I, ctypes.POINTER(_VP), ctypes.POINTER(_SZ),
                                         ctypes.POINTER(_DeviceImages), ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
+    ("zw_vp8_decode_batch_device_resized", _I, [_VP, _I, ctypes.POINTER(_VP), ctypes.POINTER(_SZ),
+                                                ctypes.POINTER(_DeviceImages), _U32, _U32, ctypes.POINTER(_Rect),
+                                                ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
+    ("zw_dbg_resize_taps", _I, [_U32, _U32, _U32, ctypes.POINTER(ctypes.c_int32)]),
     ("zw_encode_batch_device", _I, [_VP, _I, ctypes.POINTER(_DeviceImages), _U32, _U32, _U8, _U8, _I,
                                     ctypes.POINTER(_Bytes)]),
     ("zw_pipe_set_input_device", _I, [_VP, ctypes.POINTER(_DeviceImages)]),
@@ -502,6 +512,15 @@ def dbg_tokl_frame(vp8):
     return rc, m.value
 
 
+def dbg_resize_taps(src, dst, o):
+    """Test hook (CPU only): (i0, i1, f) of the resize rule for output index
+    `o` of `dst` over a source window of `src` pixels (zw_dbg_resize_taps)."""
+    L = load_library()
+    out = (ctypes.c_int32 * 3)()
+    _check(L.zw_dbg_resize_taps(int(src), int(dst), int(o), out), "dbg_resize_taps")
+    return int(out[0]), int(out[1]), int(out[2])
+
+
 def dbg_seam_stats(reset=False):
     """Test hook: the encode seam's counters (batches led, frames in them, the
     largest batch) since the last reset."""
@@ -748,6 +767,132 @@ def decode_webp_batch_device(files, out=None, channels=3, layout="chw", dtype="u
     return decode_batch_device(vp8, out, channels, layout, dtype, upsampling, scale, bias, ctx)
 
 
+def decode_batch_device_resized_ptr(frames, ptr, capacity, out_w, out_h, windows=None, channels=3, layout="chw",
+                                    dtype="u8", upsampling=UpsamplingMethod.Bilinear, scale=None, bias=None,
+                                    frame_stride=None, plane_stride=None, row_stride=None, ctx=None):
+    """zw_vp8_decode_batch_device_resized, raw-pointer form: n VP8 key frames,
+    which may differ in size, cropped and resized into n images of `out_w` x
+    `out_h` in device memory at `ptr` (`capacity` elements of `dtype`),
+    addressed as decode_batch_device_ptr's; strides left None are the packed
+    ones for the output size.  windows: None (whole frames) or one (x, y, w, h)
+    per frame, in frame pixels (None entries = that whole frame).
+
+    The values follow one integer rule (include/zwebp.h): bilinear, half-pixel
+    centres, no antialiasing, taps inside the window, over the bytes
+    decode_rgb_batch gives for the whole frame.  u8 holds (S + 32768) >> 16;
+    f32 holds float32(S / 65536) * scale[c] + bias[c] (rounded multiply,
+    rounded add), f16 that value rounded to nearest even.  A window of the
+    output's size gives decode_batch_device's values.
+
+    Frames are grouped by size and each group is one decode pass: a batch
+    costs one pass per distinct size.  Returns [(width, height)], the frames'
+    source sizes, once every write has completed."""
+    c = _ctx(ctx)
+    L = c._lib
+    arrs = [_as_u8(d) for d in frames]
+    n = len(arrs)
+    if n == 0:
+        raise ValueError("no frames")
+    lay = _layout_code(layout)
+    frame_stride, plane_stride, row_stride = _packed_strides(lay, int(out_w), int(out_h), int(channels), frame_stride,
+                                                             plane_stride, row_stride)
+    out = _DeviceImages(int(ptr), int(capacity), lay, _dtype_code(dtype), int(channels), int(upsampling),
+                        int(frame_stride), int(plane_stride or 0), int(row_stride),
+                        (ctypes.c_float * 4)(*_vec4(scale, 1.0)), (ctypes.c_float * 4)(*_vec4(bias, 0.0)))
+    rects = None
+    if windows is not None:
+        if len(windows) != n:
+            raise ValueError("one window per frame")
+        rects = (_Rect * n)()
+        for i, r in enumerate(windows):
+            if r is None:
+                fw, fh = vp8_frame_dims(arrs[i])
+                r = (0, 0, fw, fh)
+            rects[i] = _Rect(*[int(v) for v in r])
+    ptrs = (ctypes.c_void_p * n)(*[a.ctypes.data for a in arrs])
+    lens = (ctypes.c_size_t * n)(*[a.size for a in arrs])
+    ws, hs = (ctypes.c_uint32 * n)(), (ctypes.c_uint32 * n)()
+    _check(L.zw_vp8_decode_batch_device_resized(c.handle, n, ptrs, lens, ctypes.byref(out), int(out_w), int(out_h),
+                                                rects, ws, hs), "decode_batch_device_resized", DecodingError)
+    return [(ws[i], hs[i]) for i in range(n)]
+
+
+def decode_batch_device_resized(frames, size=None, out=None, windows=None, channels=3, layout="chw", dtype="u8",
+                                upsampling=UpsamplingMethod.Bilinear, scale=None, bias=None, ctx=None):
+    """n VP8 key frames, which may differ in size, cropped (windows) and
+    resized to one size straight into a torch tensor on the context's device
+    (zw_vp8_decode_batch_device_resized; the values and `windows` are
+    decode_batch_device_resized_ptr's).  No full-size RGB tensor is made.
+    Frames are grouped by size and each group is one decode pass: a batch
+    costs one pass per distinct size.
+
+    size = (H, W).  out=None: allocates and returns torch.empty [N, C, H, W]
+    (layout "chw") or [N, H, W, C] ("hwc") of `dtype` with `channels` 3 or 4.
+    out = a 4-d tensor: size (may then be None; else it must match), layout,
+    dtype, channels and strides come from it under decode_batch_device's rules
+    (innermost stride 1; rows, planes and frames may be padded; ValueError
+    otherwise).  torch's current stream is synchronised before the call; the
+    call returns with every write complete.  As for decode_batch_device, torch
+    must initialise its HIP runtime before libzwebp.so loads in the process."""
+    import torch
+    c = _ctx(ctx)
+    arrs = [_as_u8(d) for d in frames]
+    n = len(arrs)
+    if n == 0:
+        raise ValueError("no frames")
+    tdt = {0: torch.uint8, 1: torch.float16, 2: torch.float32}
+    dev = torch.device("cuda", c.device)
+    if size is not None:
+        h, w = int(size[0]), int(size[1])
+        if h <= 0 or w <= 0:
+            raise ValueError("size = (H, W), both positive")
+    if out is None:
+        if size is None:
+            raise ValueError("size = (H, W) or an out tensor")
+        lay, dt = _layout_code(layout), _dtype_code(dtype)
+        if lay not in (0, 1) or dt not in tdt or channels not in (3, 4):
+            raise ValueError("layout hwc | chw, dtype u8 | f16 | f32, channels 3 | 4")
+        out = torch.empty((n, channels, h, w) if lay == 1 else (n, h, w, channels), dtype=tdt[dt], device=dev)
+    if not isinstance(out, torch.Tensor) or out.dim() != 4:
+        raise ValueError("out must be a 4-d torch tensor")
+    if not out.is_cuda or out.device.index != c.device:
+        raise ValueError(f"out must be on cuda:{c.device}")
+    dts = [k for k, v in tdt.items() if v == out.dtype]
+    if not dts:
+        raise ValueError("out must be uint8, float16 or float32")
+    sh, st = tuple(out.shape), tuple(out.stride())
+    fits_chw = sh[0] == n and sh[1] in (3, 4) and (size is None or (sh[2], sh[3]) == (h, w))
+    fits_hwc = sh[0] == n and sh[3] in (3, 4) and (size is None or (sh[1], sh[2]) == (h, w))
+    if fits_chw and fits_hwc:
+        fits_chw = _layout_code(layout) == 1
+    if fits_chw:
+        lay, ch, h, w, fs, ps, rs, unit = 1, sh[1], sh[2], sh[3], st[0], st[1], st[2], (st[3],)
+    elif fits_hwc:
+        lay, ch, h, w, fs, ps, rs, unit = 0, sh[3], sh[1], sh[2], st[0], 0, st[1], (1 if st[2] == sh[3] else 0, st[3])
+    else:
+        raise ValueError(f"out must be [{n}, C, H, W] or [{n}, H, W, C] of `size` with C = 3 or 4")
+    if any(u != 1 for u in unit) or min(fs, ps, rs) < 0 or h <= 0 or w <= 0:
+        raise ValueError("out: only rows, planes and frames may be padded (innermost stride 1)")
+    capacity = out.untyped_storage().nbytes() // out.element_size() - out.storage_offset()
+    torch.cuda.current_stream(dev).synchronize()
+    decode_batch_device_resized_ptr(arrs, out.data_ptr(), capacity, w, h, windows, ch, lay, dts[0], upsampling, scale,
+                                    bias, fs, ps, rs, ctx=c)
+    return out
+
+
+def decode_webp_batch_device_resized(files, size=None, out=None, windows=None, channels=3, layout="chw", dtype="u8",
+                                     upsampling=UpsamplingMethod.Bilinear, scale=None, bias=None, ctx=None):
+    """decode_batch_device_resized over lossy WebP files: each RIFF container
+    is stripped with webp_parse, as decode_webp_batch_device does (ALPH, VP8L
+    and animated files raise DecodingError code 5)."""
+    vp8 = []
+    for f in files:
+        a = _as_u8(f)
+        info = webp_parse(a)
+        vp8.append(a[info["vp8_offset"]:info["vp8_offset"] + info["vp8_len"]])
+    return decode_batch_device_resized(vp8, size, out, windows, channels, layout, dtype, upsampling, scale, bias, ctx)
+
+
 def _packed_strides(lay, width, height, channels, frame_stride, plane_stride, row_stride):
     if row_stride is None:
         row_stride = width * channels if lay == 0 else width
@@ -870,6 +1015,16 @@ def webp_frame_width(vp8):
     0 for a frame too short to hold one (the decode then reports the error)."""
     a = _as_u8(vp8)
     return int(a[6]) | ((int(a[7]) & 0x3F) << 8) if a.size >= 10 else 0
+
+
+def vp8_frame_dims(vp8):
+    """(width, height) of a VP8 key-frame header (the 14-bit fields; the
+    scaling bits are dropped), (0, 0) for a frame too short to hold them.
+    What a caller needs to choose windows for decode_batch_device_resized."""
+    a = _as_u8(vp8)
+    if a.size < 10:
+        return 0, 0
+    return int(a[6]) | ((int(a[7]) & 0x3F) << 8), int(a[8]) | ((int(a[9]) & 0x3F) << 8)
 
 
 def _decode_into(data, output, stride_bytes, bpp, ctx):

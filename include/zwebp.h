@@ -253,6 +253,65 @@ typedef struct {
 } zw_device_images;
 int zw_vp8_decode_batch_device(zw_ctx *ctx, int n, const uint8_t *const *data, const size_t *lens,
                                const zw_device_images *out, uint32_t *width, uint32_t *height);
+/* Device-resident decode with crop and resize (new): n VP8 key frames, which
+ * may differ in size, into one batch of out_w x out_h images in the caller's
+ * device memory.  `out` describes n frames of out_w x out_h exactly as above
+ * (addressing, stride bounds, no overlap, capacity, device pointer).  A
+ * sibling of the conversion kernel (k_yuv2rgb_resize) writes only the wanted
+ * output pixels and converts only the source pixels they need: no full-size
+ * RGB image is made.
+ *
+ * Source image: p(y, x, c) = the byte zw_vp8_decode_rgb_batch gives for the
+ * whole frame (fill_rgb / fill_rgba, `upsampling`; channel 3 = 255).  Frame
+ * i's window windows[i] = (x, y, w, h) is in frame pixels; windows == NULL
+ * takes whole frames.  The fancy upsampler's chroma taps clamp at the frame's
+ * edges, so a window is a slice of the full-frame image, not a decode of a
+ * smaller picture.
+ *
+ * Resampling: bilinear, half-pixel centres, no antialiasing, all in integers.
+ * One axis, a window of src pixels to dst outputs, output index o (64-bit
+ * arithmetic; positions in 1/256 pixel):
+ *     pos = floor((2*o + 1) * src * 128 / dst) - 128
+ *     pos = clamp(pos, 0, (src - 1) * 256)
+ *     i0 = pos >> 8;  f = pos & 255;  i1 = min(i0 + 1, src - 1)
+ * With (x0, x1, fx) from (window w, out_w, ox) and (y0, y1, fy) from (window
+ * h, out_h, oy), output pixel (oy, ox) of channel c has
+ *     S = (256-fy) * ((256-fx) * p(y+y0, x+x0, c) + fx * p(y+y0, x+x1, c))
+ *       +      fy  * ((256-fx) * p(y+y1, x+x0, c) + fx * p(y+y1, x+x1, c))
+ * (at most 255 * 65536), stored as
+ *   ZW_DTYPE_U8   (S + 32768) >> 16;
+ *   ZW_DTYPE_F32  v = (float)S * 2^-16 (both steps exact), then v * scale[c] +
+ *                 bias[c], a rounded multiply then a rounded add (never fused);
+ *   ZW_DTYPE_F16  that float converted round-to-nearest-even.
+ * Taps never leave the window (crop then resize = resize of the crop); a
+ * window of the output's size reproduces zw_vp8_decode_batch_device's values
+ * (f = 0, i0 = o); src = 2 * dst averages pixel pairs (i0 = 2o, f = 128).
+ *
+ * Mixed sizes: the frames are grouped by (width, height), in frame order, and
+ * each group runs as one decode pass, so a batch costs one pass per distinct
+ * size; no decode kernel differs.
+ *
+ * Checked before anything is queued, each failure ZW_EINVAL: NULL arguments;
+ * out_w or out_h 0 (or above 2^20); a bad layout, dtype, channels or
+ * upsampling; strides, capacity or `data` as above; a window with w == 0, h
+ * == 0, x + w > the frame's width or y + h > its height.  A frame whose header
+ * cannot give dimensions is not refused here: the decode reports its own
+ * code.  On error the output's contents are unspecified and nothing queued
+ * outlives the call; when several frames fail, which frame's code is returned
+ * is unspecified.  The call returns after every write has completed.  The
+ * timing entries report the groups' sums (zw_decode_rgb_kernel_ms:
+ * k_yuv2rgb_resize's launches; download and fan-out 0).  widths / heights (n
+ * each, may be NULL) receive the frames' source sizes. */
+typedef struct { uint32_t x, y, w, h; } zw_rect;
+int zw_vp8_decode_batch_device_resized(zw_ctx *ctx, int n, const uint8_t *const *data, const size_t *lens,
+                                       const zw_device_images *out, uint32_t out_w, uint32_t out_h,
+                                       const zw_rect *windows /* n entries, or NULL = whole frames */,
+                                       uint32_t *widths, uint32_t *heights /* n each, may be NULL: source sizes */);
+/* Test hook, host only (no device work): the resampling rule's taps for one
+ * axis, out = (i0, i1, f) for output index o of dst over a window of src
+ * pixels, from the function the kernel runs (csrc/zw_resize.h).  ZW_EINVAL for
+ * src == 0, src > 2^23, dst == 0, o >= dst or a NULL out. */
+int zw_dbg_resize_taps(uint32_t src, uint32_t dst, uint32_t o, int32_t out[3]);
 /* Device-resident encode (new): n frames of one size read straight from the
  * caller's device memory, a batch tensor described as above (`upsampling` must
  * be 0; the same addressing, stride bounds and non-overlap rule).  Nothing
