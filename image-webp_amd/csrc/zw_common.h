@@ -125,3 +125,14 @@ struct ZwY2rDev {
 struct ZwResizeFrame {
     uint32_t slot, cx, cy, cw, ch, pad[3];
 };
+
+// The antialiased resize's per-frame weight tables (k_resize_aa_weights writes
+// them, k_yuv2rgb_resize_aa reads them): frame f's block starts f * stride
+// 32-bit words into the table area; the fields are word offsets into a block.
+// Per axis: first[dst] and count[dst] (int32) of zw_resize_aa_span, then the
+// u16 weights tap-major, weight k of output o at [k * dst + o], with room for
+// kx / ky taps per output (ceil(2 max(frame size, dst) / dst), which bounds
+// every window of the frame).
+struct ZwAaTables {
+    uint32_t stride, xfirst, xcount, yfirst, ycount, xw, yw, kx, ky;
+};

@@ -9,6 +9,7 @@
 //   device: k_dec_recon (dequant, iWHT, iDCT, prediction) and k_loopfilter.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <memory>
@@ -36,6 +37,10 @@ hipError_t zwk_yuv2rgb_dev(hipStream_t s, const uint8_t* Y, const uint8_t* U, co
 hipError_t zwk_yuv2rgb_resize(hipStream_t s, const uint8_t* Y, const uint8_t* U, const uint8_t* V, size_t ysz,
                               size_t csz, int w, int h, int ys, int cs, int layout, int dtype, int channels, int fancy,
                               void* out, const ZwY2rDev* P, const ZwResizeFrame* tab, int ow, int oh, int nframes);
+hipError_t zwk_yuv2rgb_resize_aa(hipStream_t s, const uint8_t* Y, const uint8_t* U, const uint8_t* V, size_t ysz,
+                                 size_t csz, int w, int h, int ys, int cs, int layout, int dtype, int channels, int fancy,
+                                 void* out, const ZwY2rDev* P, const ZwResizeFrame* tab, uint32_t* tables,
+                                 const ZwAaTables* L, int ow, int oh, int nframes);
 hipError_t zwk_dec_rows(hipStream_t s, int phase, const uint8_t* recs, const uint32_t* moff, const uint64_t* fbase,
                         const void* quant, uint8_t* Y, uint8_t* U, uint8_t* V, uint8_t* flags, const ZwFilterParams* fp,
                         int mbw, int mbh, size_t ysz, size_t csz, int nframes, int* rowsync, uint8_t* borders, int rows);
@@ -1336,14 +1341,21 @@ namespace {
 // slots of the caller's batch.  tab[i] = the group's frame i (its slot in the
 // batch and its window); a chunk's entries are uploaded in stream order into
 // the chunk's own scratch (lay.extra), which lives until the chunk has finished.
+// filter ZW_RESIZE_TRIANGLE_AA: the weight kernel and k_yuv2rgb_resize_aa
+// instead, with each frame's weight tables (aa) in that scratch after the
+// chunk's entries.
 struct ResizeSink : DecSink {
     size_t w = 0, h = 0;  // the group's frame size
     int out_w = 0, out_h = 0;
-    int layout = 0, dtype = 0, channels = 0, fancy = 0;
+    int layout = 0, dtype = 0, channels = 0, fancy = 0, filter = ZW_RESIZE_BILINEAR;
     uint8_t* data = nullptr;
     ZwY2rDev P = {};
+    ZwAaTables aa = {};
     std::vector<ZwResizeFrame> tab;
-    size_t extra_per_frame() const override { return sizeof(ZwResizeFrame); }
+    size_t extra_per_frame() const override
+    {
+        return sizeof(ZwResizeFrame) + (filter == ZW_RESIZE_TRIANGLE_AA ? (size_t)aa.stride * 4 : 0);
+    }
     int enqueue(zw_ctx* ctx, DecChunk& C) override
     {
         const DecMeta& M = C.meta;
@@ -1352,9 +1364,16 @@ struct ResizeSink : DecSink {
         hipStream_t s = ctx_stream(ctx);
         ZwResizeFrame* d_tab = (ZwResizeFrame*)(C.d + C.lay.extra);
         HIPOK(hipMemcpyAsync(d_tab, tab.data() + C.first, (size_t)M.n * sizeof(ZwResizeFrame), hipMemcpyHostToDevice, s));
-        HIPOK(zwk_yuv2rgb_resize(s, C.d + C.lay.y, C.d + C.lay.u, C.d + C.lay.v, M.ysz, M.csz, (int)w, (int)h,
-                                 M.mbw * 16, M.mbw * 8, layout, dtype, channels, fancy, data, &P, d_tab, out_w, out_h,
-                                 M.n));
+        if (filter == ZW_RESIZE_TRIANGLE_AA) {
+            uint32_t* d_aa = (uint32_t*)(d_tab + M.n);  // (32-byte entries: the tables stay 16-byte aligned)
+            HIPOK(zwk_yuv2rgb_resize_aa(s, C.d + C.lay.y, C.d + C.lay.u, C.d + C.lay.v, M.ysz, M.csz, (int)w, (int)h,
+                                        M.mbw * 16, M.mbw * 8, layout, dtype, channels, fancy, data, &P, d_tab, d_aa,
+                                        &aa, out_w, out_h, M.n));
+        } else {
+            HIPOK(zwk_yuv2rgb_resize(s, C.d + C.lay.y, C.d + C.lay.u, C.d + C.lay.v, M.ysz, M.csz, (int)w, (int)h,
+                                     M.mbw * 16, M.mbw * 8, layout, dtype, channels, fancy, data, &P, d_tab, out_w,
+                                     out_h, M.n));
+        }
         HIPOK(hipEventRecord(C.set->ev[DEC_EV_CALLER], s));
         return ZW_OK;
     }
@@ -1364,13 +1383,36 @@ struct ResizeSink : DecSink {
     bool place(const DecChunk&, const uint8_t*, int) override { return true; }
 };
 
+// The weight tables of one frame of w x h (any window of it) to ow x oh
+// (ZwAaTables, zw_common.h): per axis first and count per output index, then
+// ceil(2 max(size, out) / out) u16 weights per output index.  false: too large
+// for 32-bit word offsets.
+static bool aa_tables(size_t w, size_t h, size_t ow, size_t oh, ZwAaTables* L)
+{
+    const size_t kx = (2 * std::max(w, ow) + ow - 1) / ow, ky = (2 * std::max(h, oh) + oh - 1) / oh;
+    size_t o = 0;
+    L->xfirst = (uint32_t)o, o += ow;
+    L->xcount = (uint32_t)o, o += ow;
+    L->yfirst = (uint32_t)o, o += oh;
+    L->ycount = (uint32_t)o, o += oh;
+    L->xw = (uint32_t)o, o += (kx * ow + 1) / 2;
+    L->yw = (uint32_t)o, o += (ky * oh + 1) / 2;
+    o = (o + 3) & ~(size_t)3;
+    L->stride = (uint32_t)o;
+    L->kx = (uint32_t)kx;
+    L->ky = (uint32_t)ky;
+    return o < ((size_t)1 << 30);
+}
+
 }  // namespace
 
-extern "C" int zw_vp8_decode_batch_device_resized(zw_ctx* ctx, int n, const uint8_t* const* data, const size_t* lens,
-                                                  const zw_device_images* out, uint32_t out_w, uint32_t out_h,
-                                                  const zw_rect* windows, uint32_t* widths, uint32_t* heights)
+extern "C" int zw_vp8_decode_batch_device_resized_ex(zw_ctx* ctx, int n, const uint8_t* const* data,
+                                                     const size_t* lens, const zw_device_images* out, uint32_t out_w,
+                                                     uint32_t out_h, const zw_rect* windows, uint32_t* widths,
+                                                     uint32_t* heights, int filter)
 {
     if (!ctx || n <= 0 || !data || !lens || !out || !out->data) return ZW_EINVAL;
+    if (filter != ZW_RESIZE_BILINEAR && filter != ZW_RESIZE_TRIANGLE_AA) return ZW_EINVAL;
     if (out_w == 0 || out_h == 0 || out_w > (1u << 20) || out_h > (1u << 20)) return ZW_EINVAL;
     if (!device_format_ok(out)) return ZW_EINVAL;
     for (int i = 0; i < n; i++)
@@ -1391,6 +1433,8 @@ extern "C" int zw_vp8_decode_batch_device_resized(zw_ctx* ctx, int n, const uint
         if (windows && (r.w == 0 || r.h == 0)) return ZW_EINVAL;
         if (dims && ((uint64_t)r.x + r.w > (uint64_t)w || (uint64_t)r.y + r.h > (uint64_t)h)) return ZW_EINVAL;
         win[i] = ZwResizeFrame{(uint32_t)i, r.x, r.y, r.w, r.h, {0, 0, 0}};
+        ZwAaTables t;  // (a frame's weight tables must fit 32-bit offsets: also before anything is queued)
+        if (filter == ZW_RESIZE_TRIANGLE_AA && !aa_tables((size_t)w, (size_t)h, out_w, out_h, &t)) return ZW_ENOMEM;
     }
     std::vector<std::vector<int>> groups;
     {
@@ -1423,6 +1467,8 @@ extern "C" int zw_vp8_decode_batch_device_resized(zw_ctx* ctx, int n, const uint
         sink.fancy = out->upsampling == ZW_UPSAMPLE_BILINEAR;
         sink.data = (uint8_t*)out->data;
         sink.P = device_strides(out);
+        sink.filter = filter;
+        if (filter == ZW_RESIZE_TRIANGLE_AA) (void)aa_tables(sink.w, sink.h, out_w, out_h, &sink.aa);  // (checked above)
         std::vector<const uint8_t*> gdata(idx.size());
         std::vector<size_t> glens(idx.size());
         sink.tab.resize(idx.size());
@@ -1451,6 +1497,14 @@ extern "C" int zw_vp8_decode_batch_device_resized(zw_ctx* ctx, int n, const uint
         if (heights) heights[i] = key[i] >> 16;
     }
     return ZW_OK;
+}
+
+extern "C" int zw_vp8_decode_batch_device_resized(zw_ctx* ctx, int n, const uint8_t* const* data, const size_t* lens,
+                                                  const zw_device_images* out, uint32_t out_w, uint32_t out_h,
+                                                  const zw_rect* windows, uint32_t* widths, uint32_t* heights)
+{
+    return zw_vp8_decode_batch_device_resized_ex(ctx, n, data, lens, out, out_w, out_h, windows, widths, heights,
+                                                 ZW_RESIZE_BILINEAR);
 }
 
 extern "C" int zw_vp8_decode_rgb(zw_ctx* ctx, const uint8_t* vp8, size_t len, int bpp, int upsampling, zw_bytes* out,

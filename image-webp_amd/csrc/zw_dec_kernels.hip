@@ -1682,3 +1682,261 @@ extern "C" hipError_t zwk_yuv2rgb_resize(hipStream_t s, const uint8_t* Y, const 
     const dim3 grid(((unsigned)oh + rows_per_block - 1) / rows_per_block, ((unsigned)ow + 63) / 64, (unsigned)nframes);
     return hipLaunchKernel(fn, grid, dim3(64, ZW_RSZ_WAVES), args, 0, s);
 }
+
+// ---------------------------------------------------------------------------
+// The antialiased resize (zw_vp8_decode_batch_device_resized_ex with
+// ZW_RESIZE_TRIANGLE_AA): the same source image, windows, elements and strides
+// as k_yuv2rgb_resize, resampled by zw_resize.h's triangle rule, whose support
+// widens with the downscale factor.  Two kernels per chunk.
+//
+// k_resize_aa_weights: one thread per output index of either axis of a frame
+// writes that index's first tap, tap count and 12-bit weights into the frame's
+// tables (ZwAaTables, in the chunk's scratch), so the 64-bit divisions of the
+// normalisation happen once per output index, not per source pixel.
+//
+// k_yuv2rgb_resize_aa: source-row streaming.  A workgroup owns ZW_AA_COLS
+// output columns (one per lane) of ZW_AA_ROWS output rows of one frame.  It
+// walks the source rows that band needs once, ZW_AA_SROWS rows a step: all
+// lanes convert the span of those rows that the column block needs into LDS
+// (runs of 8 pixels from aligned word loads, as k_yuv2rgb_dev converts them),
+// then each lane sums its column's horizontal taps from
+// LDS (weights tap-major in the table, so a wave's load is one run of u16) and
+// adds wy * H into the u32 accumulators of the output rows whose support
+// covers that source row.  The y weights are the same in every lane: one lane
+// per (source row of the step, output row) loads its weight, 0 where the row
+// is not covered, and an unrolled wave-uniform test on the broadcast value
+// (readlane) picks the covering rows, so the accumulators are registers with
+// constant indices.  Every tap
+// loop runs over the table's counts: a span wider than ZW_AA_SPAN pixels is
+// taken in pieces, the horizontal sums carried across them.  The LDS is two
+// buffers, so a step costs one barrier.  Elements past out_w / out_h and
+// padding are never written.  Every sum is exact in u32 (zw_resize.h).
+// ---------------------------------------------------------------------------
+#define ZW_AA_COLS 256   // output columns per workgroup = its threads
+#define ZW_AA_ROWS 16    // output rows per workgroup
+#define ZW_AA_SROWS 2    // source rows per step
+#define ZW_AA_TAPS 6     // horizontal taps per turn of the tap loop
+#define ZW_AA_SPAN 2040  // source pixels of one row in LDS at a time (+ up to 8 of alignment: 2048 words)
+
+__global__ __launch_bounds__(256) void k_resize_aa_weights(const ZwResizeFrame* __restrict__ tab,
+                                                           uint32_t* __restrict__ tables, ZwAaTables L, int ow, int oh)
+{
+    const int f = blockIdx.y;
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= (uint32_t)ow + (uint32_t)oh) return;
+    const ZwResizeFrame W = tab[f];
+    uint32_t* B = tables + (size_t)f * L.stride;
+    const bool xa = t < (uint32_t)ow;
+    const uint32_t o = xa ? t : t - (uint32_t)ow, src = xa ? W.cw : W.ch, dst = xa ? (uint32_t)ow : (uint32_t)oh;
+    ZwAaSpan s = zw_resize_aa_span(src, dst, o);
+    const uint32_t cap = xa ? L.kx : L.ky;  // (the host sized the table for ceil(2m / dst) taps of any window)
+    if ((uint32_t)s.count > cap) s.count = (int32_t)cap;
+    ((int32_t*)B)[(xa ? L.xfirst : L.yfirst) + o] = s.first;
+    ((int32_t*)B)[(xa ? L.xcount : L.ycount) + o] = s.count;
+    uint16_t* wt = (uint16_t*)(B + (xa ? L.xw : L.yw));
+    zw_resize_aa_weights(src, dst, o, s, [&](int32_t k, uint32_t wk) { wt[(size_t)k * dst + o] = (uint16_t)wk; });
+}
+
+// Frame columns [A0, A1) of frame row r as RGBA words into dst, dst[0] = column
+// A0 (a multiple of 8; 16-byte aligned LDS): thread t takes the runs of 8 pixels
+// at A0 + 8 (t + 256 n), each as k_yuv2rgb_dev converts one (aligned word loads
+// of Y and of the chroma rows, y2r_row8's packed arithmetic) and writes it as
+// two 16-byte LDS stores; the partial run at the frame's right edge takes the
+// per-pixel form.  Up to 7 columns past A1 may be written (inside the buffer:
+// the caller rounds its size up to 8), none past the frame's width.
+template <bool FANCY>
+__device__ __forceinline__ void aa_fill_row(uint32_t* __restrict__ dst, const uint8_t* __restrict__ Y,
+                                            const uint8_t* __restrict__ U, const uint8_t* __restrict__ V, int w, int ys,
+                                            int cs, int cw1, int ch1, int r, int A0, int A1)
+{
+    int mr, sr;  // the row's main and secondary chroma rows (yuv2rgb_px)
+    if (FANCY) {
+        const int k = (r + 1) >> 1;
+        mr = (r & 1) ? k - 1 : k;
+        sr = max(min((r & 1) ? k : k - 1, ch1), 0);
+    } else {
+        mr = sr = r >> 1;
+    }
+    for (int x = A0 + 8 * (int)threadIdx.x; x < A1; x += 8 * ZW_AA_COLS) {
+        uint32_t* d = dst + (x - A0);
+        if (x + 8 <= w) {
+            const bool lok = x > 0, rok = (x >> 1) + 4 <= cw1;
+            const int c1 = x >> 1, c0 = lok ? c1 - 4 : c1, c2 = rok ? c1 + 4 : c1;
+            int um[6], us[6], vm[6], vs[6];
+            y2r_cols(U + (size_t)mr * cs, c0, c1, c2, lok, rok, um);
+            y2r_cols(V + (size_t)mr * cs, c0, c1, c2, lok, rok, vm);
+            if (FANCY) {
+                y2r_cols(U + (size_t)sr * cs, c0, c1, c2, lok, rok, us);
+                y2r_cols(V + (size_t)sr * cs, c0, c1, c2, lok, rok, vs);
+            }
+            const uint2 yy = *(const uint2*)(Y + (size_t)r * ys + x);
+            uint32_t px[8];
+            y2r_row8<FANCY>(yy, um, FANCY ? us : um, vm, FANCY ? vs : vm, px);
+            ((zu4*)d)[0] = zu4{px[0], px[1], px[2], px[3]};
+            ((zu4*)d)[1] = zu4{px[4], px[5], px[6], px[7]};
+        } else {
+            for (int k = 0; x + k < w; k++) d[k] = yuv2rgb_px<FANCY>(Y, U, V, ys, cs, cw1, ch1, r, x + k);
+        }
+    }
+}
+
+template <int CH, bool FANCY, int LAYOUT, class E>
+__global__ __launch_bounds__(ZW_AA_COLS) void k_yuv2rgb_resize_aa(
+    const uint8_t* __restrict__ Y, const uint8_t* __restrict__ U, const uint8_t* __restrict__ V, size_t ysz, size_t csz,
+    int w, int h, int ys, int cs, E* __restrict__ out, ZwY2rDev P, const ZwResizeFrame* __restrict__ tab,
+    const uint32_t* __restrict__ tables, ZwAaTables L, int ow, int oh)
+{
+    constexpr int ROWS = ZW_AA_ROWS, SR = ZW_AA_SROWS, SPAN = ZW_AA_SPAN, BUF = ZW_AA_SPAN + 8;
+    static_assert(SPAN % 8 == 0, "a buffer row starts on a run of 8 pixels");
+    __shared__ __attribute__((aligned(16))) uint32_t lds[2][SR][BUF];
+    auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };  // (the same in every lane: a scalar register)
+    const int f = blockIdx.z;
+    const int ox0 = (int)blockIdx.y * ZW_AA_COLS, ox = ox0 + (int)threadIdx.x;
+    const int oy0 = (int)blockIdx.x * ROWS;
+    const ZwResizeFrame W = tab[f];
+    const uint32_t* B = tables + (size_t)f * L.stride;
+    const int32_t *xfirst = (const int32_t*)B + L.xfirst, *xcount = (const int32_t*)B + L.xcount;
+    const int32_t *yfirst = (const int32_t*)B + L.yfirst, *ycount = (const int32_t*)B + L.ycount;
+    const uint16_t *xw = (const uint16_t*)(B + L.xw), *yw = (const uint16_t*)(B + L.yw);
+    const bool live = ox < ow;
+    const int xf = live ? xfirst[ox] : 0, xc = live ? xcount[ox] : 0;
+    // what the block needs, in window pixels: columns [xs0, xs1), rows [ys0, ys1)
+    const int oxl = min(ox0 + ZW_AA_COLS, ow) - 1, oyl = min(oy0 + ROWS, oh) - 1;
+    const int xs0 = uni(xfirst[ox0]), xs1 = uni(xfirst[oxl] + xcount[oxl]);
+    const int ys0 = uni(yfirst[oy0]), ys1 = uni(yfirst[oyl] + ycount[oyl]);
+    // the y taps: lane 16 r + j of each wave looks after source row r of a step and output row oy0 + j
+    static_assert(SR * ROWS <= 64 && ROWS == 16, "one lane per (source row of a step, output row)");
+    const int lr = (int)(threadIdx.x & 63u) >> 4, lj = (int)threadIdx.x & 15;
+    const bool lrow = lr < SR && oy0 + lj < oh;
+    const int lyf = lrow ? yfirst[oy0 + lj] : 0, lyc = lrow ? ycount[oy0 + lj] : 0;
+    Y += (size_t)f * ysz;
+    U += (size_t)f * csz;
+    V += (size_t)f * csz;
+    const int cw1 = ((w + 1) >> 1) - 1, ch1 = ((h + 1) >> 1) - 1;
+    uint32_t acc[ROWS][CH];
+#pragma unroll
+    for (int j = 0; j < ROWS; j++)
+#pragma unroll
+        for (int c = 0; c < CH; c++) acc[j][c] = 0;
+    int step = 0;
+    for (int i0 = ys0; i0 < ys1; i0 += SR) {
+        uint32_t H[SR][CH];
+#pragma unroll
+        for (int r = 0; r < SR; r++)
+#pragma unroll
+            for (int c = 0; c < CH; c++) H[r][c] = 0;
+        // this step's y weights, one load per wave, asked for before the rows are converted: 0 where
+        // the output row's support does not cover the source row
+        uint32_t wyv = 0;
+        {
+            const uint32_t t = (uint32_t)(i0 + lr - lyf);
+            if (i0 + lr < ys1 && t < (uint32_t)lyc) wyv = yw[(size_t)t * oh + (oy0 + lj)];
+        }
+        for (int cb = xs0; cb < xs1; cb += SPAN, step++) {
+            const int ce = min(cb + SPAN, xs1);
+            const int A0 = ((int)W.cx + cb) & ~7;  // the buffer's first frame column
+            uint32_t* buf = &lds[step & 1][0][0];
+#pragma unroll
+            for (int r = 0; r < SR; r++)
+                if (i0 + r < ys1)
+                    aa_fill_row<FANCY>(buf + r * BUF, Y, U, V, w, ys, cs, cw1, ch1, (int)W.cy + i0 + r, A0,
+                                       (int)W.cx + ce);
+            __syncthreads();
+            const int ka = max(xf, cb), kb = min(xf + xc, ce);
+            const uint16_t* wp = xw + (size_t)(ka - xf) * ow + ox;
+            const uint32_t* bp = buf + ((int)W.cx + ka - A0);
+            // ZW_AA_TAPS taps a turn, their weights and pixels asked for together (one memory latency
+            // a turn, not one a tap); a slot past the last tap has weight 0 and rereads the last pixel
+            for (int i = ka; i < kb; i += ZW_AA_TAPS, wp += (size_t)ZW_AA_TAPS * ow, bp += ZW_AA_TAPS) {
+                uint32_t wx[ZW_AA_TAPS], px[ZW_AA_TAPS][SR];
+#pragma unroll
+                for (int u = 0; u < ZW_AA_TAPS; u++) {
+                    wx[u] = i + u < kb ? (uint32_t)wp[(size_t)u * ow] : 0u;
+                    const int at = min(u, kb - 1 - i);
+#pragma unroll
+                    for (int r = 0; r < SR; r++) px[u][r] = bp[r * BUF + at];
+                }
+#pragma unroll
+                for (int u = 0; u < ZW_AA_TAPS; u++)
+#pragma unroll
+                    for (int r = 0; r < SR; r++)
+#pragma unroll
+                        for (int c = 0; c < CH; c++) H[r][c] += __umul24(wx[u], (px[u][r] >> (8 * c)) & 255u);
+            }
+        }
+        const uint64_t covered = __builtin_amdgcn_ballot_w64(wyv != 0);  // bit 16 r + j: row j takes source row r
+#pragma unroll
+        for (int r = 0; r < SR; r++) {
+#pragma unroll
+            for (int j = 0; j < ROWS; j++) {
+                if ((covered >> (r * ROWS + j)) & 1) {  // (scalar: the same in every lane)
+                    const uint32_t wy = (uint32_t)__builtin_amdgcn_readlane((int)wyv, r * ROWS + j);
+#pragma unroll
+                    for (int c = 0; c < CH; c++) acc[j][c] += __umul24(wy, H[r][c]);
+                }
+            }
+        }
+    }
+    if (!live) return;
+    out += (size_t)W.slot * P.frame_stride + (LAYOUT == 0 ? (size_t)ox * CH : (size_t)ox);
+#pragma unroll
+    for (int j = 0; j < ROWS; j++) {
+        const int oy = oy0 + j;
+        if (oy >= oh) break;
+        E* o = out + (size_t)oy * P.row_stride;
+#pragma unroll
+        for (int c = 0; c < CH; c++)
+            o[LAYOUT == 0 ? (size_t)c : (size_t)c * P.plane_stride] =
+                rsz_elem<E>(zw_resize_aa_S(acc[j][c]), P.scale[c], P.bias[c]);
+    }
+}
+
+template <int CH, bool FANCY, int LAYOUT>
+static const void* aa_kernel_dtype(int dtype)
+{
+    if (dtype == 0) return (const void*)k_yuv2rgb_resize_aa<CH, FANCY, LAYOUT, uint8_t>;
+    if (dtype == 1) return (const void*)k_yuv2rgb_resize_aa<CH, FANCY, LAYOUT, _Float16>;
+    if (dtype == 2) return (const void*)k_yuv2rgb_resize_aa<CH, FANCY, LAYOUT, float>;
+    return nullptr;
+}
+template <int CH, bool FANCY>
+static const void* aa_kernel_layout(int layout, int dtype)
+{
+    if (layout == 0) return aa_kernel_dtype<CH, FANCY, 0>(dtype);
+    if (layout == 1) return aa_kernel_dtype<CH, FANCY, 1>(dtype);
+    return nullptr;
+}
+template <int CH>
+static const void* aa_kernel_fancy(int fancy, int layout, int dtype)
+{
+    return fancy ? aa_kernel_layout<CH, true>(layout, dtype) : aa_kernel_layout<CH, false>(layout, dtype);
+}
+
+// The two launches for nframes frames: the weight tables (tables = nframes
+// blocks of L->stride words, device memory), then the resampling kernel, coded
+// and addressed as zwk_yuv2rgb_resize.  Row bands on grid x, column blocks on
+// grid y.
+extern "C" hipError_t zwk_yuv2rgb_resize_aa(hipStream_t s, const uint8_t* Y, const uint8_t* U, const uint8_t* V,
+                                            size_t ysz, size_t csz, int w, int h, int ys, int cs, int layout, int dtype,
+                                            int channels, int fancy, void* out, const ZwY2rDev* P,
+                                            const ZwResizeFrame* tab, uint32_t* tables, const ZwAaTables* L, int ow,
+                                            int oh, int nframes)
+{
+    const void* fn = channels == 3 ? aa_kernel_fancy<3>(fancy, layout, dtype)
+                                   : (channels == 4 ? aa_kernel_fancy<4>(fancy, layout, dtype) : nullptr);
+    if (!fn || w <= 0 || h <= 0 || ow <= 0 || oh <= 0 || ow > (1 << 20) || oh > (1 << 20) || nframes <= 0)
+        return hipErrorInvalidValue;
+    ZwAaTables l = *L;
+    {
+        void* args[] = {&tab, &tables, &l, &ow, &oh};
+        const dim3 grid(((unsigned)ow + (unsigned)oh + 255) / 256, (unsigned)nframes);
+        const hipError_t e = hipLaunchKernel((const void*)k_resize_aa_weights, grid, dim3(256), args, 0, s);
+        if (e != hipSuccess) return e;
+    }
+    ZwY2rDev p = *P;
+    const uint32_t* ctables = tables;
+    void* args[] = {&Y, &U, &V, &ysz, &csz, &w, &h, &ys, &cs, &out, &p, &tab, &ctables, &l, &ow, &oh};
+    const dim3 grid(((unsigned)oh + ZW_AA_ROWS - 1) / ZW_AA_ROWS, ((unsigned)ow + ZW_AA_COLS - 1) / ZW_AA_COLS,
+                    (unsigned)nframes);
+    return hipLaunchKernel(fn, grid, dim3(ZW_AA_COLS), args, 0, s);
+}

@@ -483,6 +483,19 @@ extern "C" int zw_dbg_resize_taps(uint32_t src, uint32_t dst, uint32_t o, int32_
     return ZW_OK;
 }
 
+// zw_resize.h's antialiased taps on the host (the functions k_resize_aa_weights runs).
+extern "C" int zw_dbg_resize_aa_taps(uint32_t src, uint32_t dst, uint32_t o, int32_t* first, int32_t* count,
+                                     uint16_t* weights, int cap)
+{
+    if (!first || !count || !weights || src == 0 || dst == 0 || o >= dst || src > (1u << 23)) return ZW_EINVAL;
+    const ZwAaSpan s = zw_resize_aa_span(src, dst, o);
+    if (cap < s.count) return ZW_EINVAL;
+    *first = s.first;
+    *count = s.count;
+    zw_resize_aa_weights(src, dst, o, s, [&](int32_t k, uint32_t w) { weights[k] = (uint16_t)w; });
+    return ZW_OK;
+}
+
 extern "C" int zw_dbg_tokl_frame(const uint8_t* vp8, size_t len, int* match)
 {
     if (!match || (!vp8 && len)) return ZW_EINVAL;

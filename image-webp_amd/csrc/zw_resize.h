@@ -1,8 +1,10 @@
-// zw_resize.h -- the resampling rule of zw_vp8_decode_batch_device_resized, one
-// definition for the host (validation, zw_dbg_resize_taps), the device
-// (k_yuv2rgb_resize) and, restated in numpy, the tests (include/zwebp.h gives
-// the rule in full).  Bilinear, half-pixel centres, no antialiasing; integers
-// only, so every user computes the same bits.
+// zw_resize.h -- the resampling rules of zw_vp8_decode_batch_device_resized[_ex],
+// one definition each for the host (validation, zw_dbg_resize_taps,
+// zw_dbg_resize_aa_taps), the device (k_yuv2rgb_resize; k_resize_aa_weights and
+// k_yuv2rgb_resize_aa) and, restated in numpy, the tests (include/zwebp.h gives
+// the rules in full).  First the two-tap rule: bilinear, half-pixel centres, no
+// antialiasing; then the antialiased triangle rule.  Integers only, so every
+// user computes the same bits.
 #pragma once
 #include <stdint.h>
 
@@ -54,3 +56,69 @@ ZW_RSZ_HD uint32_t zw_resize_sum(uint32_t p00, uint32_t p01, uint32_t p10, uint3
 ZW_RSZ_HD uint32_t zw_resize_u8(uint32_t S) { return (S + 32768u) >> 16; }
 // S as the float the float dtypes scale and bias: both steps are exact.
 ZW_RSZ_HD float zw_resize_f32(uint32_t S) { return (float)S * (1.0f / 65536.0f); }
+
+// ---------------------------------------------------------------------------
+// The antialiased rule (ZW_RESIZE_TRIANGLE_AA; include/zwebp.h gives it in
+// full): a triangle filter whose support widens with the downscale factor,
+// taps outside the window dropped and the rest renormalised to 12 bits.  One
+// axis, a window of src pixels to dst outputs, output index o, m = max(src,
+// dst); positions in 1/(2 dst) pixel, so everything is an integer.  Source
+// sample i sits at (2i + 1) dst, the output centre at c = (2o + 1) src, and
+// u_i = max(0, 2m - |(2i + 1) dst - c|).  The host hook (zw_dbg_resize_aa_taps)
+// and the weight kernel (k_resize_aa_weights) both run the functions below.
+// src <= 2^23 and dst <= 2^32 keep every product below 2^63.
+// ---------------------------------------------------------------------------
+#define ZW_AA_ONE 4096u  // the weights of one output index sum to this
+
+// The unnormalised weight of window pixel i (may be <= 0 outside the support).
+ZW_RSZ_HD int64_t zw_resize_aa_u(uint32_t src, uint32_t dst, uint32_t o, int64_t i)
+{
+    const int64_t m = src > dst ? src : dst;
+    const int64_t t = (2 * i + 1) * (int64_t)dst - (2 * (int64_t)o + 1) * (int64_t)src;
+    return 2 * m - (t < 0 ? -t : t);
+}
+
+// The taps of output index o: the contiguous run first .. first + count - 1 of
+// the i in [0, src - 1] with u_i > 0 (never empty, at most ceil(2m / dst)
+// indices), and total = their sum U.
+struct ZwAaSpan {
+    int32_t first, count;
+    uint64_t total;
+};
+ZW_RSZ_HD ZwAaSpan zw_resize_aa_span(uint32_t src, uint32_t dst, uint32_t o)
+{
+    const int64_t m = src > dst ? src : dst, d2 = 2 * (int64_t)dst, c = (2 * (int64_t)o + 1) * (int64_t)src;
+    // u_i > 0  <=>  c - 2m < (2i + 1) dst < c + 2m
+    const int64_t lo = c - 2 * m - dst, hi = c + 2 * m - dst;  // lo < 2 dst i < hi; hi > 0
+    int64_t a = lo >= 0 ? lo / d2 + 1 : 0;
+    int64_t b = (hi + d2 - 1) / d2 - 1;
+    if (b > (int64_t)src - 1) b = (int64_t)src - 1;
+    ZwAaSpan s;
+    s.first = (int32_t)a;
+    s.count = (int32_t)(b - a + 1);
+    uint64_t U = 0;
+    for (int64_t i = a; i <= b; i++) U += (uint64_t)zw_resize_aa_u(src, dst, o, i);
+    s.total = U;
+    return s;
+}
+
+// The normalised weights w_0 .. w_(count-1) by cumulative rounding: W_k =
+// floor((C_k * 4096 + floor(U / 2)) / U) over the running sum C_k, w_k = W_k -
+// W_(k-1); they sum to exactly 4096 and none is negative.  put(k, w_k) is
+// called for k = 0 .. count - 1 in order.  (U reaches 2 src^2 / dst: 64 bits.)
+template <class Put>
+ZW_RSZ_HD void zw_resize_aa_weights(uint32_t src, uint32_t dst, uint32_t o, const ZwAaSpan& s, Put&& put)
+{
+    uint64_t C = 0;
+    uint32_t prev = 0;
+    for (int32_t k = 0; k < s.count; k++) {
+        C += (uint64_t)zw_resize_aa_u(src, dst, o, (int64_t)s.first + k);
+        const uint32_t W = (uint32_t)((C * ZW_AA_ONE + s.total / 2) / s.total);
+        put(k, W - prev);
+        prev = W;
+    }
+}
+
+// T = sum_y wy * sum_x wx * p (at most 255 * 2^24; any summation order is exact
+// in u32) as the S the storage steps above take: S = (T + 128) >> 8.
+ZW_RSZ_HD uint32_t zw_resize_aa_S(uint32_t T) { return (T + 128u) >> 8; }

@@ -160,6 +160,11 @@ SIGNATURES = [
                                                 ctypes.POINTER(_DeviceImages), _U32, _U32, ctypes.POINTER(_Rect),
                                                 ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
     ("zw_dbg_resize_taps", _I, [_U32, _U32, _U32, ctypes.POINTER(ctypes.c_int32)]),
+    ("zw_vp8_decode_batch_device_resized_ex", _I, [_VP, _I, ctypes.POINTER(_VP), ctypes.POINTER(_SZ),
+                                                   ctypes.POINTER(_DeviceImages), _U32, _U32, ctypes.POINTER(_Rect),
+                                                   ctypes.POINTER(_U32), ctypes.POINTER(_U32), _I]),
+    ("zw_dbg_resize_aa_taps", _I, [_U32, _U32, _U32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                   ctypes.POINTER(ctypes.c_uint16), _I]),
     ("zw_encode_batch_device", _I, [_VP, _I, ctypes.POINTER(_DeviceImages), _U32, _U32, _U8, _U8, _I,
                                     ctypes.POINTER(_Bytes)]),
     ("zw_pipe_set_input_device", _I, [_VP, ctypes.POINTER(_DeviceImages)]),
@@ -521,6 +526,20 @@ def dbg_resize_taps(src, dst, o):
     return int(out[0]), int(out[1]), int(out[2])
 
 
+def dbg_resize_aa_taps(src, dst, o):
+    """Test hook (CPU only): (first, [weights]) of the antialiased resize rule
+    for output index `o` of `dst` over a source window of `src` pixels
+    (zw_dbg_resize_aa_taps): the taps first .. first + len(weights) - 1 and
+    their 12-bit weights, which sum to 4096."""
+    L = load_library()
+    src, dst, o = int(src), int(dst), int(o)
+    cap = (2 * max(src, dst) + dst - 1) // dst if dst > 0 else 1
+    first, count = ctypes.c_int32(0), ctypes.c_int32(0)
+    w = (ctypes.c_uint16 * max(cap, 1))()
+    _check(L.zw_dbg_resize_aa_taps(src, dst, o, ctypes.byref(first), ctypes.byref(count), w, cap), "dbg_resize_aa_taps")
+    return int(first.value), [int(w[k]) for k in range(count.value)]
+
+
 def dbg_seam_stats(reset=False):
     """Test hook: the encode seam's counters (batches led, frames in them, the
     largest batch) since the last reset."""
@@ -769,8 +788,8 @@ def decode_webp_batch_device(files, out=None, channels=3, layout="chw", dtype="u
 
 def decode_batch_device_resized_ptr(frames, ptr, capacity, out_w, out_h, windows=None, channels=3, layout="chw",
                                     dtype="u8", upsampling=UpsamplingMethod.Bilinear, scale=None, bias=None,
-                                    frame_stride=None, plane_stride=None, row_stride=None, ctx=None):
-    """zw_vp8_decode_batch_device_resized, raw-pointer form: n VP8 key frames,
+                                    frame_stride=None, plane_stride=None, row_stride=None, ctx=None, antialias=False):
+    """zw_vp8_decode_batch_device_resized_ex, raw-pointer form: n VP8 key frames,
     which may differ in size, cropped and resized into n images of `out_w` x
     `out_h` in device memory at `ptr` (`capacity` elements of `dtype`),
     addressed as decode_batch_device_ptr's; strides left None are the packed
@@ -783,6 +802,12 @@ def decode_batch_device_resized_ptr(frames, ptr, capacity, out_w, out_h, windows
     f32 holds float32(S / 65536) * scale[c] + bias[c] (rounded multiply,
     rounded add), f16 that value rounded to nearest even.  A window of the
     output's size gives decode_batch_device's values.
+
+    antialias=True takes the triangle filter instead (ZW_RESIZE_TRIANGLE_AA,
+    include/zwebp.h): its support widens with the downscale factor, as PIL's
+    and interpolate(mode="bilinear", antialias=True)'s does, in integers with
+    12-bit weights; u8 / f32 / f16 store S = (T + 128) >> 8 as above.  An int
+    is passed as the C entry's `filter` unchanged.
 
     Frames are grouped by size and each group is one decode pass: a batch
     costs one pass per distinct size.  Returns [(width, height)], the frames'
@@ -812,19 +837,21 @@ def decode_batch_device_resized_ptr(frames, ptr, capacity, out_w, out_h, windows
     ptrs = (ctypes.c_void_p * n)(*[a.ctypes.data for a in arrs])
     lens = (ctypes.c_size_t * n)(*[a.size for a in arrs])
     ws, hs = (ctypes.c_uint32 * n)(), (ctypes.c_uint32 * n)()
-    _check(L.zw_vp8_decode_batch_device_resized(c.handle, n, ptrs, lens, ctypes.byref(out), int(out_w), int(out_h),
-                                                rects, ws, hs), "decode_batch_device_resized", DecodingError)
+    filt = int(antialias)  # False / True = ZW_RESIZE_BILINEAR / ZW_RESIZE_TRIANGLE_AA
+    _check(L.zw_vp8_decode_batch_device_resized_ex(c.handle, n, ptrs, lens, ctypes.byref(out), int(out_w), int(out_h),
+                                                   rects, ws, hs, filt), "decode_batch_device_resized", DecodingError)
     return [(ws[i], hs[i]) for i in range(n)]
 
 
 def decode_batch_device_resized(frames, size=None, out=None, windows=None, channels=3, layout="chw", dtype="u8",
-                                upsampling=UpsamplingMethod.Bilinear, scale=None, bias=None, ctx=None):
+                                upsampling=UpsamplingMethod.Bilinear, scale=None, bias=None, ctx=None, antialias=False):
     """n VP8 key frames, which may differ in size, cropped (windows) and
     resized to one size straight into a torch tensor on the context's device
     (zw_vp8_decode_batch_device_resized; the values and `windows` are
     decode_batch_device_resized_ptr's).  No full-size RGB tensor is made.
     Frames are grouped by size and each group is one decode pass: a batch
-    costs one pass per distinct size.
+    costs one pass per distinct size.  antialias=True: the triangle filter
+    (decode_batch_device_resized_ptr), what a loader that downscales wants.
 
     size = (H, W).  out=None: allocates and returns torch.empty [N, C, H, W]
     (layout "chw") or [N, H, W, C] ("hwc") of `dtype` with `channels` 3 or 4.
@@ -876,12 +903,13 @@ def decode_batch_device_resized(frames, size=None, out=None, windows=None, chann
     capacity = out.untyped_storage().nbytes() // out.element_size() - out.storage_offset()
     torch.cuda.current_stream(dev).synchronize()
     decode_batch_device_resized_ptr(arrs, out.data_ptr(), capacity, w, h, windows, ch, lay, dts[0], upsampling, scale,
-                                    bias, fs, ps, rs, ctx=c)
+                                    bias, fs, ps, rs, ctx=c, antialias=antialias)
     return out
 
 
 def decode_webp_batch_device_resized(files, size=None, out=None, windows=None, channels=3, layout="chw", dtype="u8",
-                                     upsampling=UpsamplingMethod.Bilinear, scale=None, bias=None, ctx=None):
+                                     upsampling=UpsamplingMethod.Bilinear, scale=None, bias=None, ctx=None,
+                                     antialias=False):
     """decode_batch_device_resized over lossy WebP files: each RIFF container
     is stripped with webp_parse, as decode_webp_batch_device does (ALPH, VP8L
     and animated files raise DecodingError code 5)."""
@@ -890,7 +918,8 @@ def decode_webp_batch_device_resized(files, size=None, out=None, windows=None, c
         a = _as_u8(f)
         info = webp_parse(a)
         vp8.append(a[info["vp8_offset"]:info["vp8_offset"] + info["vp8_len"]])
-    return decode_batch_device_resized(vp8, size, out, windows, channels, layout, dtype, upsampling, scale, bias, ctx)
+    return decode_batch_device_resized(vp8, size, out, windows, channels, layout, dtype, upsampling, scale, bias, ctx,
+                                       antialias)
 
 
 def _packed_strides(lay, width, height, channels, frame_stride, plane_stride, row_stride):

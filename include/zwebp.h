@@ -312,6 +312,54 @@ int zw_vp8_decode_batch_device_resized(zw_ctx *ctx, int n, const uint8_t *const 
  * pixels, from the function the kernel runs (csrc/zw_resize.h).  ZW_EINVAL for
  * src == 0, src > 2^23, dst == 0, o >= dst or a NULL out. */
 int zw_dbg_resize_taps(uint32_t src, uint32_t dst, uint32_t o, int32_t out[3]);
+/* The same entry with a choice of resampling filter (new).  Every argument,
+ * check, grouping rule, error behaviour and timing entry is the one above;
+ * `filter` is checked with the others (any value not listed: ZW_EINVAL before
+ * anything is queued).  zw_vp8_decode_batch_device_resized is this entry with
+ * ZW_RESIZE_BILINEAR.
+ *
+ * ZW_RESIZE_BILINEAR: the two-tap rule above, no antialiasing (it aliases
+ * below half size, as interpolate(antialias=False) does).
+ *
+ * ZW_RESIZE_TRIANGLE_AA: a triangle filter whose support widens with the
+ * downscale factor, taps outside the window dropped and the rest renormalised:
+ * what PIL and interpolate(mode="bilinear", antialias=True) compute, in
+ * integers, so every summation order gives the same bits.  One axis, a window
+ * of s source pixels to d outputs, output index o, m = max(s, d); positions in
+ * units of 1/(2d) pixel:
+ *     source sample i sits at (2i + 1) * d, the output centre at c = (2o + 1) * s
+ *     u_i = max(0, 2m - |(2i + 1) * d - c|)
+ * The taps are the i in [0, s - 1] with u_i > 0: a contiguous, never empty run
+ * of at most ceil(2m / d) indices (at most 2m + d over the whole axis).  They
+ * are normalised to 12 bits by cumulative rounding: in increasing i, with the
+ * running sum C_k = u_first + ... + u_k and the total U,
+ *     W_k = floor((C_k * 4096 + floor(U / 2)) / U),  w_k = W_k - W_(k-1),  W_(-1) = 0
+ * (64-bit: U reaches about 2 s^2 / d), so the weights sum to exactly 4096 and
+ * none is negative.  With the x taps and weights from (window w, out_w, ox)
+ * and the y ones from (window h, out_h, oy), channel c of output pixel (oy, ox)
+ * has
+ *     T = sum_y wy * sum_x wx * p(y, x, c)
+ * over the same source image p as above (T <= 255 * 2^24, every partial sum
+ * below the total: exact in 32 bits in any order), and
+ *     S = (T + 128) >> 8
+ * is stored exactly as the S above (u8, f32 with scale and bias, f16).
+ * s == d gives one tap of weight 4096 at i = o, so a window of the output's
+ * size reproduces zw_vp8_decode_batch_device's values; s == 2d gives 512,
+ * 1536, 1536, 512 on 2o - 1 .. 2o + 2, renormalised at the window's ends; s < d
+ * is plain bilinear with 12-bit weights; taps never leave the window.
+ * A weight kernel writes each frame's per-axis tables once; a streaming kernel
+ * (k_yuv2rgb_resize_aa) reads every needed source row once.
+ * zw_decode_rgb_kernel_ms reports both kernels' time. */
+enum { ZW_RESIZE_BILINEAR = 0, ZW_RESIZE_TRIANGLE_AA = 1 };
+int zw_vp8_decode_batch_device_resized_ex(zw_ctx *ctx, int n, const uint8_t *const *data, const size_t *lens,
+                                          const zw_device_images *out, uint32_t out_w, uint32_t out_h,
+                                          const zw_rect *windows, uint32_t *widths, uint32_t *heights, int filter);
+/* Test hook, host only: the antialiased rule's taps for one axis, from the
+ * functions the weight kernel runs (csrc/zw_resize.h).  *first = the first tap,
+ * *count = their number, weights[0 .. count) = w_k.  ZW_EINVAL for src == 0,
+ * src > 2^23, dst == 0, o >= dst, a NULL pointer or cap < count. */
+int zw_dbg_resize_aa_taps(uint32_t src, uint32_t dst, uint32_t o, int32_t *first, int32_t *count, uint16_t *weights,
+                          int cap);
 /* Device-resident encode (new): n frames of one size read straight from the
  * caller's device memory, a batch tensor described as above (`upsampling` must
  * be 0; the same addressing, stride bounds and non-overlap rule).  Nothing

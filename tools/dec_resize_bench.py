@@ -17,7 +17,12 @@ k_yuv2rgb_dev for full_interp, beside torch's device time for the interpolate sl
 The two routes resample by different rules (the fused one in integers, torch in floats),
 so the tool reports their largest difference, not equality.
 
-    python tools/dec_resize_bench.py [frames=1024] [--reps 5] [--out FILE]
+--antialias runs the same three legs with antialiasing on both routes: the fused legs
+through antialias=True (k_resize_aa_weights + k_yuv2rgb_resize_aa, the triangle rule),
+full_interp through interpolate(antialias=True); the result then also carries the fused
+kernels' device time over k_yuv2rgb_dev's on the same frames.
+
+    python tools/dec_resize_bench.py [frames=1024] [--reps 5] [--antialias] [--out FILE]
 """
 import argparse
 import json
@@ -34,6 +39,7 @@ sys.path.insert(0, os.path.join(ROOT, "image-webp_amd"))
 ap = argparse.ArgumentParser()
 ap.add_argument("frames", nargs="?", type=int, default=1024)
 ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--antialias", action="store_true")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 
@@ -66,7 +72,7 @@ out_mixed = torch.empty((F, 3, OH, OW), dtype=torch.float16, device=dev)
 
 
 def fused():
-    zwebp.decode_batch_device_resized(vp8, None, out_fused, scale=scale, bias=bias, ctx=ctx)
+    zwebp.decode_batch_device_resized(vp8, None, out_fused, scale=scale, bias=bias, ctx=ctx, antialias=a.antialias)
 
 
 interp_ms = []  # device time of the interpolate and copy slices (torch events)
@@ -78,14 +84,14 @@ def full_interp():
     e0.record()
     for i in range(0, F, 128):
         out_interp[i:i + 128] = torch.nn.functional.interpolate(full[i:i + 128], size=(OH, OW), mode="bilinear",
-                                                                antialias=False, align_corners=False)
+                                                                antialias=a.antialias, align_corners=False)
     e1.record()
     torch.cuda.synchronize()
     interp_ms.append(e0.elapsed_time(e1))
 
 
 def fused_mixed():
-    zwebp.decode_batch_device_resized(mixed, None, out_mixed, scale=scale, bias=bias, ctx=ctx)
+    zwebp.decode_batch_device_resized(mixed, None, out_mixed, scale=scale, bias=bias, ctx=ctx, antialias=a.antialias)
 
 
 legs = [("fused", fused), ("full_interp", full_interp), ("fused_mixed", fused_mixed)]
@@ -103,7 +109,9 @@ for _ in range(a.reps):
         kernel_ms[name].append(zwebp.decode_rgb_kernel_ms(ctx=ctx))
 
 diff = (out_fused.float() - out_interp.float()).abs()
-res = {"workload": f"{F} frames {w}x{h} Q75 m4 (8 distinct synth_rgba images) -> {OW}x{OH} CHW f16, "
+FUSED_KERNEL = "k_resize_aa_weights + k_yuv2rgb_resize_aa" if a.antialias else "k_yuv2rgb_resize"
+res = {"antialias": bool(a.antialias),
+       "workload": f"{F} frames {w}x{h} Q75 m4 (8 distinct synth_rgba images) -> {OW}x{OH} CHW f16, "
                    f"{a.reps} alternating repeats; fused_mixed: {F} frames of "
                    + ", ".join(f"{sw}x{sh}" for sw, sh in SIZES) + " interleaved",
        "legs": {}}
@@ -112,12 +120,14 @@ for name, _ in legs:
     res["legs"][name] = {"wall_ms": [round(x, 1) for x in m], "median_ms": round(statistics.median(m), 1),
                          "min_ms": round(min(m), 1), "max_ms": round(max(m), 1),
                          "decodes_per_s_median": round(F / statistics.median(m) * 1e3, 1),
-                         "rgb_kernel": "k_yuv2rgb_dev" if name == "full_interp" else "k_yuv2rgb_resize",
+                         "rgb_kernel": "k_yuv2rgb_dev" if name == "full_interp" else FUSED_KERNEL,
                          "rgb_kernel_ms": [round(x, 3) for x in k],
                          "rgb_kernel_ms_median": round(statistics.median(k), 3)}
 res["legs"]["full_interp"]["interpolate_device_ms"] = [round(x, 3) for x in interp_ms]
 res["legs"]["full_interp"]["interpolate_device_ms_median"] = round(statistics.median(interp_ms), 3)
 res["fused_over_full_interp"] = round(statistics.median(ms["full_interp"]) / statistics.median(ms["fused"]), 3)
+res["fused_kernel_ms_over_yuv2rgb_dev_ms"] = round(statistics.median(kernel_ms["fused"])
+                                                   / statistics.median(kernel_ms["full_interp"]), 3)
 res["fused_vs_interp_max_abs_diff"] = round(float(diff.max()), 4)
 res["fused_vs_interp_mean_abs_diff"] = round(float(diff.mean()), 6)
 res["full_size_tensor_bytes"] = full.numel() * full.element_size()
