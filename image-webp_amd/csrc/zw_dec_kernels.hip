@@ -389,7 +389,10 @@ DI uint32_t recon_row_quad(const int x[4], int q, bool nz, bool any_nz, int c0, 
 {
     int o[4] = {0, 0, 0, 0};
     if (any_nz) idct_quad_exact(x[0], x[1], x[2], x[3], q, o);
-    const int d = (c0 + 4) >> 3;
+    // DC-only is i32 in the reference (transform.rs:13-16): c0 from a large Y2 block puts
+    // (c0 + 4) >> 3 past i16, so it is clamped before it is packed -- onto a prediction
+    // in 0..255, +-255 gives the same clamped sum as any larger value
+    const int d = min(max((c0 + 4) >> 3, -255), 255);
     const uint32_t R01 = nz ? pack_lo(o[0], o[1]) : pack_lo(d, d);
     const uint32_t R32 = nz ? pack_lo(o[3], o[2]) : pack_lo(d, d);
     const uint32_t t01 = __builtin_amdgcn_perm(0u, T, 0x0c010c00u), t32 = __builtin_amdgcn_perm(0u, T, 0x0c020c03u);

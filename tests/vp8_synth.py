@@ -12,6 +12,7 @@ fields and a list of macroblocks.
                    the two byte for byte)
   write_keyframe   params + mbs -> the 'VP8 ' payload
   random_mbs       uniform modes on every MB, heavy-tailed levels
+  wide_mbs         the same modes, levels by band of |level * dequantiser| past 2047
   default_params   a header with nothing optional in it
 
 `params` (every field of the first partition's header, s9.2-9.11, s19.2):
@@ -343,7 +344,12 @@ def write_keyframe(params, mbs):
     return bytes(out)
 
 
-LEVEL_BUDGET = 2047  # per block, sum of |level * dequantiser| (so each product stays within it too)
+# Per block, the cap on the sum of |level * dequantiser| in random_mbs (so each
+# product stays within it too).  Up to here libwebp and the reference agree and
+# libwebp pins the planes; what lies beyond (products up to 2114 * 440, the
+# reference's 16-bit iDCT and its i32 DC-only path) is wide_mbs' ground, pinned
+# by the oracle alone: tests/golden/wide_*.vp8, tests/test_wide_coeffs.py.
+LEVEL_BUDGET = 2047
 
 
 def _magnitude(rng):
@@ -400,6 +406,116 @@ def random_mbs(params, seed, density=0.35, skip_frac=0.25, empty_frac=0.12):
                 left -= v * q
                 levels[b][n] = -v if s < 0.5 else v
         mbs.append(dict(segment=segment, skip=skip, ymode=ymode, bmodes=bmodes, uvmode=uvmode, levels=levels))
+    return mbs
+
+
+# ---- beyond LEVEL_BUDGET: levels placed by band of m = |level * dequantiser|
+WIDE_BANDS = ("wrap", "sat", "dconly", "cat6")
+MAX_LEVEL = 3 + (8 << 3) + 2047  # 2114, the largest level DCT category 6 can carry
+I16_MAX = 32767
+# Y2 levels (zigzag order from 0) of the three smallest MBs found, at index 127
+# (y2dc 314, y2ac 440), whose DC-only residual (c0 + 4) >> 3 leaves the i16 range
+HAND_Y2 = ((2114,) * 3, (-2114,) * 3, (2114,) * 5)
+
+
+def hand_mb(which):
+    """I16 DC / chroma DC, not skipped, nothing but HAND_Y2[which] in the Y2 block."""
+    levels = np.zeros((25, 16), np.int64)
+    levels[24][:len(HAND_Y2[which])] = HAND_Y2[which]
+    return dict(segment=0, skip=0, ymode=0, bmodes=[0] * 16, uvmode=0, levels=levels)
+
+
+def edge_levels(q):
+    """The levels whose product with q is +-32767 or +-32768, or the nearest on either side of them."""
+    return sorted({v for t in (I16_MAX, I16_MAX + 1) for v in (t // q, t // q + 1) if 1 <= v <= MAX_LEVEL})
+
+
+def _wide_level(rng, band, q):
+    """A signed level for the dequantiser q: its product in the band, or in the
+    nearest one that q can reach.  wrap never saturates (-32768 is still an i16)."""
+    neg = rng.random() < 0.5
+    u = rng.random()
+    edges = edge_levels(q)
+    if band == "cat6":
+        v = int(rng.integers(512, MAX_LEVEL + 1))
+    elif band != "wrap" and u < 0.15:
+        v = MAX_LEVEL
+    elif u < 0.30 and edges:
+        v = int(rng.choice(edges))
+        if band == "wrap" and v * q == I16_MAX + 1:
+            neg = True
+        elif band == "wrap" and v * q > I16_MAX:
+            v = I16_MAX // q
+    elif band != "wrap" and u < 0.85 and q * MAX_LEVEL > I16_MAX:
+        v = int(rng.integers(I16_MAX // q + 1, MAX_LEVEL + 1))
+    else:
+        m = int(rng.integers(24000, I16_MAX + 1) if rng.random() < 0.5 else rng.integers(2048, I16_MAX + 1))
+        v = min(max((m + q // 2) // q, -(-2048 // q)), min(MAX_LEVEL, I16_MAX // q))
+    return -v if neg else v
+
+
+def wide_mbs(params, seed, band, density=0.3, skip_frac=0.15, empty_frac=0.1, force=None, hand=()):
+    """Modes as in random_mbs (uniform, skipped and empty MBs among them); levels
+    by band of the dequantised magnitude m = |level * dequantiser|:
+      wrap    2048 <= m <= 32767: no input of the 16-bit iDCT saturates (at most 7
+              Y2 coefficients, so the iWHT's outputs stay within i16 as well), the
+              sums inside its butterflies pass +-32767 and wrap
+      sat     m > 32767 wherever the dequantiser reaches it, level +-2114 often
+      dconly  mostly I16 MBs with no luma AC tokens (a few blocks of some carry
+              them) under a Y2 block of 1..16 large levels, so that the DC-only
+              residual (c0 + 4) >> 3 crosses +-32768 and +-65536; B_PRED MBs get
+              luma blocks of one wide DC level
+      cat6    levels 512..2114 whatever the product, often at the first and the
+              last scan position
+    wrap and sat place the exact edges (edge_levels) often.  `force` = {ymode,
+    bmodes, uvmode} fixes every MB's modes and leaves none skipped or empty;
+    `hand` = [[MB index, n], ...] puts hand_mb(n) there."""
+    assert band in WIDE_BANDS
+    rng = np.random.default_rng(seed)
+    mbw, mbh = (params["width"] + 15) // 16, (params["height"] + 15) // 16
+    seg = params["segments"]
+    dq = dequant_factors(params)
+    hand = {int(k): int(n) for k, n in hand}
+    mbs = []
+    for k in range(mbw * mbh):
+        segment = int(rng.integers(0, 4)) if seg and seg["update_map"] else 0
+        ymode = int(rng.integers(0, 4 if band == "dconly" and rng.random() < 0.6 else 5))
+        bmodes = [int(v) for v in rng.integers(0, 10, 16)]
+        uvmode = int(rng.integers(0, 4))
+        skip = int(params["skip_prob"] is not None and rng.random() < skip_frac)
+        empty = rng.random() < empty_frac
+        some_ac = rng.random() < 0.3
+        if force:
+            ymode, bmodes, uvmode, skip, empty = force["ymode"], list(force["bmodes"]), force["uvmode"], 0, False
+        levels = np.zeros((25, 16), np.int64)
+        ydc, yac, y2dc, y2ac, uvdc, uvac = dq[segment]
+        for b in range(25):
+            dc, ac = (ydc, yac) if b < 16 else ((uvdc, uvac) if b < 24 else (y2dc, y2ac))
+            first = 1 if (b < 16 and ymode != B_PRED) else 0
+            draws = rng.random(18)
+            if skip or empty or (b == 24 and ymode == B_PRED):
+                continue
+            pos = [n for n in range(first, 16) if draws[n] < density * (1.0 - n / 24.0)]
+            if band == "dconly" and b == 24:
+                n = (1, 2, 3, 4, 5, 6, 8, 12, 16)[int(draws[16] * 9)]
+                pos = list(range(n)) if draws[17] < 0.5 else sorted(int(v) for v in rng.permutation(16)[:n])
+            elif band == "dconly" and b < 16:
+                pos = [0] if ymode == B_PRED else (pos if some_ac and draws[16] < 0.25 else [])
+            elif draws[16] < 0.2:
+                continue
+            elif band == "cat6":
+                pos = sorted(set(pos[:3]) | ({first} if draws[17] < 0.5 else set()) | ({15} if draws[0] < 0.3 else set()))
+            elif band == "wrap" and b == 24:
+                pos = pos[:7]
+            for n in pos:
+                q = dc if n == 0 else ac
+                if band == "dconly" and b == 24:
+                    v = int(rng.integers(1500, MAX_LEVEL + 1)) * (-1 if rng.random() < 0.5 else 1)
+                else:
+                    v = _wide_level(rng, "wrap" if band == "dconly" and b < 16 and ymode != B_PRED else band, q)
+                levels[b][n] = v
+        mb = dict(segment=segment, skip=skip, ymode=ymode, bmodes=bmodes, uvmode=uvmode, levels=levels)
+        mbs.append(hand_mb(hand[k]) if k in hand else mb)
     return mbs
 
 

@@ -1,6 +1,6 @@
 // dec_header_dump.cpp -- what the decoder's CPU code (csrc/zw_dec_parse.cpp)
-// makes of a key frame, as plain numbers for tests/test_synth_streams.py: the
-// header fields, the per-segment dequantisers, the loop filter's table (built
+// makes of a key frame, as plain numbers for tests/test_synth_streams.py and
+// tests/test_wide_coeffs.py: the header fields, the per-segment dequantisers, the loop filter's table (built
 // from the header the way the decode paths build it) and, per macroblock, the
 // modes and levels of the packed records.  One "frame" line, one "probs" line
 // and one "mb" line per macroblock for each .vp8 file given.

@@ -12,7 +12,14 @@ and V planes from the system libwebp (WebPDecodeYUV), the independent decoder.
 The oracle's decode must give the same digests, or the stream is listed in
 ORACLE_PINNED below with the line of the reference's decoder that decides it.
 
-Needs oracle/liboracle.so (make -C oracle) and the system libwebp.
+A second family, tests/golden/wide_*.vp8 with tests/golden/decode_wide.json,
+holds the coefficients past +-2047 (vp8_synth.wide_mbs: bands wrap, sat, dconly,
+cat6).  libwebp differs from the reference there and is not consulted; every
+entry is pinned by the oracle.  tests/test_wide_coeffs.py states what the
+family must keep holding.
+
+Needs oracle/liboracle.so (make -C oracle) and the system libwebp (`--wide`
+writes the second family alone and needs no libwebp).
 """
 import copy
 import json
@@ -131,12 +138,79 @@ STREAMS = [
 ]
 
 
+# The second family, wide_*: levels by band of |level * dequantiser| beyond
+# LEVEL_BUDGET (vp8_synth.wide_mbs).  libwebp is known to differ there, so it is
+# not consulted: the oracle pins every one of them.
+WIDE_REASON = ("coefficients past +-2047: decoder/vp8.rs:326, :951 keep and dequantise them as i32; the iWHT "
+               "(common/transform.rs:82-114), the DC-only shortcut (transform.rs:13-16, chosen at vp8.rs:1110-1117) and "
+               "the residue's addition (common/prediction.rs:138-152) are i32; only the full iDCT "
+               "(common/transform_simd_intrinsics.rs:478-632) saturates its input to i16 and wraps")
+I127 = dict(yac=127)  # all six dequantisers at index 127: 157, 284, 314, 440, 132, 284
+DC_FORM = dict(ymode=0, bmodes=[0] * 16, uvmode=0)        # one MB: prediction 128 throughout
+BDC_FORM = dict(ymode=4, bmodes=[0] * 16, uvmode=0)       # one MB: B_DC sub-blocks under 127 above, 129 left
+WIDE = [
+    # 80 x 48: per band no filter / the normal filter at 30 or more / the simple filter
+    ("wrap_lf0", MAIN, dict(yac=60, skip_prob=128), dict(band="wrap")),
+    # (segment quantisers 87, 113, 57, 27: yac 128, 217, 64, 31 give products of exactly -32768 and +-32767)
+    ("wrap_normal_seg", MAIN, dict(filter_level=32, sharpness=2, skip_prob=100,
+                                   segments=seg(quant=(87, 113, 57, 27), lf=(30, 40, 50, 63))), dict(band="wrap")),
+    ("wrap_simple_p4", MAIN, dict(filter_type=1, filter_level=35, yac=90, log2_nparts=2, ydc_delta=-6, uvac_delta=9),
+     dict(band="wrap")),
+    ("sat_lf0", MAIN, dict(skip_prob=128, **I127), dict(band="sat")),
+    ("sat_normal", MAIN, dict(filter_level=40, sharpness=1, **I127), dict(band="sat")),
+    ("sat_simple_seg", MAIN, dict(filter_type=1, filter_level=30, skip_prob=90, ydc_delta=-2,
+                                  segments=seg(quant=(127, 113, 87, 57), lf=(20, 30, 45, 63))), dict(band="sat")),
+    ("dconly_lf0", MAIN, I127, dict(band="dconly", hand=[[0, 0], [7, 1], [14, 2]])),
+    ("dconly_normal", MAIN, dict(filter_level=45, skip_prob=128, **I127), dict(band="dconly")),
+    ("dconly_simple_seg", MAIN, dict(filter_type=1, filter_level=30, skip_prob=128,
+                                     segments=seg(quant=(127, 110, 90, 70), lf=(10, 25, 40, 63))), dict(band="dconly")),
+    ("cat6_lf0", MAIN, dict(yac=0, skip_prob=128), dict(band="cat6")),
+    ("cat6_normal", MAIN, dict(filter_level=30, yac=10, y2dc_delta=5, y2ac_delta=-10, uvdc_delta=10, uvac_delta=-5),
+     dict(band="cat6")),
+    ("cat6_simple_seg_p4", MAIN, dict(filter_type=1, filter_level=33, skip_prob=128, log2_nparts=2,
+                                      segments=seg(quant=(0, 5, 12, 20), lf=(15, 30, 45, 60))), dict(band="cat6")),
+    # partial MBs; the hand-built Y2 MBs through the device token parse (two columns, one partition)
+    ("sat_37x21", (37, 21), dict(filter_level=36, sharpness=3, skip_prob=128, uvdc_delta=-4,
+                                 segments=seg(quant=(127, 115, 125, 80), lf=(30, 36, 50, 63))), dict(band="sat")),
+    ("hand_32x16", (32, 16), I127, dict(band="dconly", hand=[[0, 0], [1, 1]])),
+]
+# 16 x 16, one MB, no filter: the three hand-built MBs, then band x form x quantiser index
+WIDE += [(f"mb_hand{n}", (16, 16), I127, dict(band="dconly", hand=[[0, n]])) for n in range(3)]
+MB_YAC = dict(wrap=(30, 50, 70, 87, 113, 127), sat=(127, 125, 115, 100, 80, 60), dconly=(127, 127, 120, 110, 100, 90),
+              cat6=(0, 4, 8, 12, 16, 20))
+WIDE += [(f"mb_{band}_{fname}{i}", (16, 16), dict(yac=yac), dict(band=band, force=form, density=0.4))
+         for band in S.WIDE_BANDS for fname, form in (("dc", DC_FORM), ("bdc", BDC_FORM))
+         for i, yac in enumerate(MB_YAC[band])]
+
+
 def build(name, size, fields, gen, seed):
     params = S.default_params(*size)
     assert set(fields) <= set(params), name
     params.update(copy.deepcopy(fields))
     gen = dict(seed=seed, **gen)
-    return params, gen, S.write_keyframe(params, S.random_mbs(params, **gen))
+    mbs = S.wide_mbs(params, **gen) if "band" in gen else S.random_mbs(params, **gen)
+    return params, gen, S.write_keyframe(params, mbs)
+
+
+def main_wide():
+    entries = []
+    for k, (name, size, fields, gen) in enumerate(WIDE):
+        name = "wide_" + name
+        params, gen, vp8 = build(name, size, fields, gen, 0x51DE0000 + k)
+        assert len(vp8) <= MAX_BYTES, (name, len(vp8))
+        rc, r = O.decode(vp8)
+        assert rc == 0, (name, rc)
+        mbw = r["mbw"]
+        digests = S.plane_digests(r["y"], r["u"], r["v"], size[0], size[1], mbw * 16, mbw * 8)
+        with open(os.path.join(OUT, name + ".vp8"), "wb") as f:
+            f.write(vp8)
+        entries.append(dict(name=name, width=size[0], height=size[1], params=params, gen=gen, yuv_sha256=digests,
+                            pinned_by="oracle", reason=WIDE_REASON))
+        print(f"{name}: {len(vp8)} bytes")
+    with open(os.path.join(OUT, "decode_wide.json"), "w") as f:
+        json.dump({"generator": "tools/make_synth_golden.py", "streams": entries}, f, indent=1)
+        f.write("\n")
+    print("wrote", len(entries), "wide streams")
 
 
 def main():
@@ -174,4 +248,6 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if "--wide" not in sys.argv[1:]:  # --wide: the second family alone (needs no libwebp)
+        main()
+    main_wide()
