@@ -120,6 +120,15 @@ struct ZwY2rDev {
     float scale[4], bias[4];
 };
 
+// The alpha kernels' per-frame table entry (zw_alpha_kernels.hip): whether the
+// chunk's frame carries an alpha plane (else channel 3 keeps 255) and its ALPH
+// filtering method (0 none, 1 horizontal, 2 vertical, 3 gradient); `plane` =
+// which of the chunk's uploaded planes is the frame's (only frames with alpha
+// have one).
+struct ZwAlphaFrame {
+    uint32_t has_alpha, filter, plane, pad;
+};
+
 // k_yuv2rgb_resize's per-frame table entry (zw_vp8_decode_batch_device_resized):
 // the frame's slot in the caller's batch and its source window in frame pixels.
 struct ZwResizeFrame {

@@ -2,7 +2,9 @@
 // feeds the host parser's packed MB records (zw_dec_parse.cpp) or the device
 // token parse's (zw_dec_tokens.hip) to the reconstruction / loop filter kernels
 // and brings the planes or packed RGB(A) back, or converts them straight into
-// the caller's device memory (zw_vp8_decode_batch_device).
+// the caller's device memory (zw_vp8_decode_batch_device), with the alpha planes
+// of lossy files that carry an ALPH chunk on request (zw_webp_decode_batch_device:
+// host zw_vp8l_dec.cpp, device zw_alpha_kernels.hip).
 //
 //   host  : zw_dec_parse.cpp (headers, modes, tokens -> one packed record per
 //           macroblock; no device code there).
@@ -24,6 +26,7 @@
 #include "zw_dec_parse.h"
 #include "zw_host_internal.h"
 #include "zw_progress.h"
+#include "zw_vp8l_dec.h"
 
 extern "C" {
 hipError_t zwk_dec_recon(hipStream_t s, const uint8_t* recs, const uint32_t* moff, const uint64_t* fbase,
@@ -57,6 +60,11 @@ hipError_t zwk_dec_tok_write(hipStream_t s, const uint8_t* blob, const ZwTokFram
                              const uint8_t* modes, const uint8_t* snaps, const int* err1, const uint32_t* moff,
                              const uint64_t* fbase, uint8_t* recs, int nmb, int n);
 size_t zw_tok1_lds_bytes(int mbw);
+size_t zw_alpha_plane_stride(size_t w, size_t h);
+hipError_t zwk_alpha_unfilter(hipStream_t s, uint8_t* planes, size_t pstride, int w, int h, int filter,
+                              const uint32_t* list, int count);
+hipError_t zwk_alpha_store(hipStream_t s, const uint8_t* planes, size_t pstride, const ZwAlphaFrame* tab, int w, int h,
+                           int layout, int dtype, void* out, const ZwY2rDev* P, int nframes);
 }
 #include "zw_tokl.h"
 
@@ -514,6 +522,10 @@ struct DecSink {
     virtual ~DecSink() {}
     // device scratch the sink needs per frame beside the planes (at lay.extra)
     virtual size_t extra_per_frame() const = 0;
+    // host work of the sink's own for the chunk's frames [first, first + cnt),
+    // started before the chunk's device work is queued (set 0 / 1 = the buffer
+    // set the chunk runs on); enqueue collects it
+    virtual void begin_chunk(zw_ctx*, int /*first*/, int /*cnt*/, int /*set*/) {}
     // checks the chunk and queues the sink's device work after the loop filter
     virtual int enqueue(zw_ctx* ctx, DecChunk& C) = 0;
     // the set's event that marks the chunk's device work done
@@ -875,6 +887,7 @@ struct DecRun {
     int launch_chunk(int c)
     {
         DecChunk& C = B[c & 1];
+        sink.begin_chunk(ctx, C.first, C.meta.n, c & 1);
         if (int r = dec_launch(ctx, K, sink.extra_per_frame() * C.meta.n, C)) return r;
         return sink.enqueue(ctx, C);
     }
@@ -1215,16 +1228,21 @@ struct DeviceSink : DecSink {
     uint8_t* data = nullptr;
     ZwY2rDev P = {};
     size_t extra_per_frame() const override { return 0; }
-    int enqueue(zw_ctx* ctx, DecChunk& C) override
+    // checks the chunk's sizes and queues the colour conversion
+    int convert(zw_ctx* ctx, DecChunk& C)
     {
         const DecMeta& M = C.meta;
         for (int i = 0; i < M.n; i++)
             if ((size_t)M.F[i].width != w || (size_t)M.F[i].height != h) return ZW_EINVAL;
-        hipStream_t s = ctx_stream(ctx);
-        HIPOK(zwk_yuv2rgb_dev(s, C.d + C.lay.y, C.d + C.lay.u, C.d + C.lay.v, M.ysz, M.csz, (int)w, (int)h, M.mbw * 16,
-                              M.mbw * 8, layout, dtype, channels, fancy,
+        HIPOK(zwk_yuv2rgb_dev(ctx_stream(ctx), C.d + C.lay.y, C.d + C.lay.u, C.d + C.lay.v, M.ysz, M.csz, (int)w, (int)h,
+                              M.mbw * 16, M.mbw * 8, layout, dtype, channels, fancy,
                               data + (size_t)C.first * P.frame_stride * elsize, &P, M.n));
-        HIPOK(hipEventRecord(C.set->ev[DEC_EV_CALLER], s));
+        return ZW_OK;
+    }
+    int enqueue(zw_ctx* ctx, DecChunk& C) override
+    {
+        if (int r = convert(ctx, C)) return r;
+        HIPOK(hipEventRecord(C.set->ev[DEC_EV_CALLER], ctx_stream(ctx)));
         return ZW_OK;
     }
     DecEv wait_event() const override { return DEC_EV_CALLER; }
@@ -1300,14 +1318,129 @@ static ZwY2rDev device_strides(const zw_device_images* out)
 
 }  // namespace
 
-extern "C" int zw_vp8_decode_batch_device(zw_ctx* ctx, int n, const uint8_t* const* data, const size_t* lens,
-                                          const zw_device_images* out, uint32_t* width, uint32_t* height)
+namespace {
+
+// zw_webp_decode_batch_device's output with ZW_WEBP_ALPHA: DeviceSink's colour
+// conversion with 4 channels, then the chunk's alpha planes.  A frame's ALPH
+// payload (alph[i]; NULL: the file has no alpha flag and keeps 255) is read on
+// the host threads (zw_alph_read, one frame per task) into pinned staging,
+// started before the chunk's device work is queued so that the two overlap;
+// enqueue uploads the chunk's table and planes into its scratch (lay.extra:
+// the ZwAlphaFrame entries, the three filters' lists of planes, the planes),
+// runs the filter kernels over each filter's planes and k_alpha_store.
+struct AlphaDeviceSink : DeviceSink {
+    const uint8_t* const* alph = nullptr;
+    const size_t* alph_len = nullptr;
+    size_t pstride = 0;
+    std::thread worker;     // the chunk's ALPH reads
+    std::vector<int> rc;    // their codes, per frame of the chunk
+    uint8_t* stage = nullptr;
+    int staged = 0, nplanes = 0, nlist[4] = {0, 0, 0, 0};
+    bool oom = false;
+    double host_ms = 0;     // written by the worker, read after its join
+    struct Ev {
+        hipEvent_t e[3];    // upload queued, filters done, store done
+    };
+    std::vector<Ev> evs;
+
+    ~AlphaDeviceSink() override
+    {
+        if (worker.joinable()) worker.join();
+        for (Ev& v : evs)
+            for (hipEvent_t e : v.e) (void)hipEventDestroy(e);
+    }
+    static size_t head_bytes(int cnt) { return (size_t)cnt * (sizeof(ZwAlphaFrame) + 16); }
+    size_t extra_per_frame() const override { return sizeof(ZwAlphaFrame) + 16 + pstride; }
+    void begin_chunk(zw_ctx* ctx, int first, int cnt, int set) override
+    {
+        if (worker.joinable()) worker.join();
+        rc.assign((size_t)cnt, ZW_OK);
+        staged = cnt;
+        nplanes = nlist[1] = nlist[2] = nlist[3] = 0;
+        int na = 0;
+        for (int i = 0; i < cnt; i++) na += alph[first + i] != nullptr;
+        stage = (uint8_t*)ctx->pin[PIN_ALPHA0 + set].reserve(head_bytes(cnt) + (size_t)na * pstride);
+        oom = stage == nullptr;
+        if (oom || na == 0) return;
+        ZwAlphaFrame* tab = (ZwAlphaFrame*)stage;
+        uint32_t* lists = (uint32_t*)(stage + (size_t)cnt * sizeof(ZwAlphaFrame));
+        for (int i = 0; i < cnt; i++) {
+            const uint8_t* a = alph[first + i];
+            if (!a) {
+                tab[i] = ZwAlphaFrame{0, 0, 0, 0};
+                continue;
+            }
+            const uint32_t filter = alph_len[first + i] ? (a[0] >> 2) & 3u : 0u;  // (an empty payload fails its read)
+            tab[i] = ZwAlphaFrame{1, filter, (uint32_t)nplanes, 0};
+            if (filter) lists[(size_t)(filter - 1) * cnt + nlist[filter]++] = (uint32_t)nplanes;
+            nplanes++;
+        }
+        worker = std::thread([this, first, cnt, tab]() {
+            const double t0 = dec_now_ms();
+            uint8_t* planes = stage + head_bytes(cnt);
+            parallel_for(cnt, [&](int i) {
+                if (!tab[i].has_alpha) return;
+                int filter = 0;
+                rc[i] = zw_alph_read(alph[first + i], alph_len[first + i], (uint32_t)w, (uint32_t)h,
+                                     planes + (size_t)tab[i].plane * pstride, &filter);
+            });
+            host_ms += dec_now_ms() - t0;
+        });
+    }
+    int enqueue(zw_ctx* ctx, DecChunk& C) override
+    {
+        if (worker.joinable()) worker.join();
+        const DecMeta& M = C.meta;
+        if (oom) return ZW_ENOMEM;
+        if (staged != M.n) return ZW_EINVAL;
+        for (int i = 0; i < M.n; i++)
+            if (rc[i]) return rc[i];
+        if (int r = DeviceSink::convert(ctx, C)) return r;
+        hipStream_t s = ctx_stream(ctx);
+        if (nplanes > 0) {
+            uint8_t* dx = C.d + C.lay.extra;
+            const size_t head = head_bytes(M.n);
+            Ev v;
+            for (hipEvent_t& e : v.e) HIPOK(hipEventCreate(&e));
+            evs.push_back(v);
+            HIPOK(hipMemcpyAsync(dx, stage, head + (size_t)nplanes * pstride, hipMemcpyHostToDevice, s));
+            HIPOK(hipEventRecord(v.e[0], s));
+            const uint32_t* d_lists = (const uint32_t*)(dx + (size_t)M.n * sizeof(ZwAlphaFrame));
+            for (int f = 1; f <= 3; f++)
+                HIPOK(zwk_alpha_unfilter(s, dx + head, pstride, (int)w, (int)h, f, d_lists + (size_t)(f - 1) * M.n, nlist[f]));
+            HIPOK(hipEventRecord(v.e[1], s));
+            HIPOK(zwk_alpha_store(s, dx + head, pstride, (const ZwAlphaFrame*)dx, (int)w, (int)h, layout, dtype,
+                                  data + (size_t)C.first * P.frame_stride * elsize, &P, M.n));
+            HIPOK(hipEventRecord(v.e[2], s));
+        }
+        HIPOK(hipEventRecord(C.set->ev[DEC_EV_CALLER], s));
+        return ZW_OK;
+    }
+    // after the run: the call's alpha times into the context
+    void collect(zw_ctx* ctx)
+    {
+        if (worker.joinable()) worker.join();
+        ctx->alpha_ms[0] = (float)host_ms;
+        for (Ev& v : evs) {
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, v.e[0], v.e[1]) == hipSuccess) ctx->alpha_ms[1] += ms;
+            if (hipEventElapsedTime(&ms, v.e[1], v.e[2]) == hipSuccess) ctx->alpha_ms[2] += ms;
+        }
+    }
+};
+
+// zw_vp8_decode_batch_device, and with `alph` (n entries) the alpha form.
+static int device_batch(zw_ctx* ctx, int n, const uint8_t* const* data, const size_t* lens, const zw_device_images* out,
+                        uint32_t* width, uint32_t* height, const uint8_t* const* alph, const size_t* alph_len)
 {
     if (!ctx || n <= 0 || !data || !lens || !out || !out->data) return ZW_EINVAL;
     if (!device_format_ok(out)) return ZW_EINVAL;
+    if (alph && out->channels != 4) return ZW_EINVAL;
     for (int i = 0; i < n; i++)
         if (!data[i] && lens[i]) return ZW_EINVAL;
-    DeviceSink sink;
+    AlphaDeviceSink asink;
+    DeviceSink dsink;
+    DeviceSink& sink = alph ? asink : dsink;
     {  // dimensions first (they bound what the kernel addresses)
         DecFrame f0;
         const int r = parse_header(f0, data[0], lens[0]);
@@ -1328,9 +1461,124 @@ extern "C" int zw_vp8_decode_batch_device(zw_ctx* ctx, int n, const uint8_t* con
     sink.fancy = out->upsampling == ZW_UPSAMPLE_BILINEAR;
     sink.data = (uint8_t*)out->data;
     sink.P = device_strides(out);
-    if (int r = DecRun(ctx, n, data, lens, sink).run()) return r;
+    if (alph) {
+        asink.alph = alph;
+        asink.alph_len = alph_len;
+        asink.pstride = zw_alpha_plane_stride(w, h);
+        ctx->alpha_ms[0] = ctx->alpha_ms[1] = ctx->alpha_ms[2] = 0.f;
+    }
+    const int r = DecRun(ctx, n, data, lens, sink).run();
+    if (alph) asink.collect(ctx);
+    if (r) return r;
     if (width) *width = (uint32_t)w;
     if (height) *height = (uint32_t)h;
+    return ZW_OK;
+}
+
+}  // namespace
+
+extern "C" int zw_vp8_decode_batch_device(zw_ctx* ctx, int n, const uint8_t* const* data, const size_t* lens,
+                                          const zw_device_images* out, uint32_t* width, uint32_t* height)
+{
+    return device_batch(ctx, n, data, lens, out, width, height, nullptr, nullptr);
+}
+
+extern "C" int zw_webp_decode_batch_device(zw_ctx* ctx, int n, const uint8_t* const* files, const size_t* lens,
+                                           int flags, const zw_device_images* out, uint32_t* width, uint32_t* height)
+{
+    if (!ctx || n <= 0 || !files || !lens || !out || !out->data || (flags & ~ZW_WEBP_ALPHA)) return ZW_EINVAL;
+    if (!device_format_ok(out)) return ZW_EINVAL;
+    const bool alpha = (flags & ZW_WEBP_ALPHA) != 0;
+    if (alpha && out->channels != 4) return ZW_EINVAL;
+    std::vector<const uint8_t*> vp8((size_t)n), alph((size_t)n, nullptr);
+    std::vector<size_t> vlen((size_t)n), alen((size_t)n, 0);
+    for (int i = 0; i < n; i++) {
+        if (!files[i] && lens[i]) return ZW_EINVAL;
+        zw_webp_info_ex info;
+        if (int r = zw_webp_parse_ex(files[i], lens[i], flags, &info)) return r;
+        vp8[i] = files[i] + info.vp8_offset;
+        vlen[i] = (size_t)info.vp8_len;
+        int fw = 0, fh = 0;  // read_image: InconsistentImageSizes (decoder/api.rs:668-670)
+        if (peek_dims(vp8[i], vlen[i], &fw, &fh) && ((uint32_t)fw != info.width || (uint32_t)fh != info.height))
+            return ZW_EINCONSISTENT_SIZES;
+        if (alpha && info.has_alpha) {
+            alph[i] = files[i] + info.alph_offset;
+            alen[i] = (size_t)info.alph_len;
+        }
+    }
+    return device_batch(ctx, n, vp8.data(), vlen.data(), out, width, height, alpha ? alph.data() : nullptr,
+                        alpha ? alen.data() : nullptr);
+}
+
+extern "C" int zw_webp_decode_ex(zw_ctx* ctx, const uint8_t* data, size_t len, int bpp, int upsampling, int flags,
+                                 zw_bytes* out, uint32_t* width, uint32_t* height)
+{
+    if (flags == 0) return zw_webp_decode(ctx, data, len, bpp, upsampling, out, width, height);
+    if (!ctx || !out || flags != ZW_WEBP_ALPHA || bpp != 4 || (!data && len)) return ZW_EINVAL;
+    out->data = nullptr;
+    out->len = 0;
+    zw_webp_info_ex info;
+    if (int r = zw_webp_parse_ex(data, len, flags, &info)) return r;
+    const size_t fbytes = (size_t)info.width * info.height * 4;
+    HIPOK(hipSetDevice(ctx->device));
+    void* d = ctx->alpha_tmp.reserve(fbytes);
+    if (!d) return ZW_ENOMEM;
+    zw_device_images img;
+    memset(&img, 0, sizeof img);
+    img.data = d;
+    img.capacity = fbytes;
+    img.layout = ZW_LAYOUT_HWC;
+    img.dtype = ZW_DTYPE_U8;
+    img.channels = 4;
+    img.upsampling = upsampling;
+    img.frame_stride = fbytes;
+    img.row_stride = (size_t)info.width * 4;
+    const uint8_t* f[1] = {data};
+    const size_t l[1] = {len};
+    uint32_t w = 0, h = 0;
+    if (int r = zw_webp_decode_batch_device(ctx, 1, f, l, flags, &img, &w, &h)) return r;
+    uint8_t* buf = frame_pool().get(fbytes);
+    if (!buf) return ZW_ENOMEM;
+    if (hipMemcpy(buf, d, fbytes, hipMemcpyDeviceToHost) != hipSuccess) {
+        if (!zw_dec_pool_put(buf)) free(buf);
+        return ZW_EDEVICE;
+    }
+    out->data = buf;
+    out->len = fbytes;
+    if (width) *width = w;
+    if (height) *height = h;
+    return ZW_OK;
+}
+
+extern "C" int zw_alph_decode(zw_ctx* ctx, const uint8_t* payload, size_t len, uint32_t width, uint32_t height,
+                              uint8_t* plane_out)
+{
+    if (!ctx || !plane_out || (!payload && len) || width == 0 || height == 0 || width > 16384 || height > 16384)
+        return ZW_EINVAL;
+    const size_t n = (size_t)width * height, pstride = zw_alpha_plane_stride(width, height);
+    HIPOK(hipSetDevice(ctx->device));
+    uint8_t* hp = (uint8_t*)ctx->pin[PIN_ALPHA0].reserve(256 + pstride);
+    if (!hp) return ZW_ENOMEM;
+    int filter = 0;
+    if (int r = zw_alph_read(payload, len, width, height, hp + 256, &filter)) return r;
+    if (filter) {
+        uint8_t* d = (uint8_t*)ctx_scratch(ctx, 256 + pstride);
+        if (!d) return ZW_ENOMEM;
+        memset(hp, 0, 256);  // the list: plane 0
+        hipStream_t s = ctx_stream(ctx);
+        HIPOK(hipMemcpyAsync(d, hp, 256 + pstride, hipMemcpyHostToDevice, s));
+        HIPOK(zwk_alpha_unfilter(s, d + 256, pstride, (int)width, (int)height, filter, (const uint32_t*)d, 1));
+        HIPOK(hipMemcpyAsync(hp + 256, d + 256, n, hipMemcpyDeviceToHost, s));
+        HIPOK(hipStreamSynchronize(s));
+    }
+    memcpy(plane_out, hp + 256, n);
+    return ZW_OK;
+}
+
+extern "C" int zw_decode_alpha_times(zw_ctx* ctx, float* ms)
+{
+    if (!ctx || !ms) return ZW_EINVAL;
+    for (int i = 0; i < 3; i++) ms[i] = ctx->alpha_ms[i];
     return ZW_OK;
 }
 

@@ -560,8 +560,9 @@ extern "C" int zw_dbg_tokl_frame(const uint8_t* vp8, size_t len, int* match)
 // WebP container, lossy subset: WebPDecoder::new -> read_data
 // (decoder/api.rs:334-510) for a simple "VP8 " file or a VP8X file whose image
 // is a VP8 chunk, then read_image (:640-700) + decode_rgb / decode_rgba
-// (:938-993).  Lossless (VP8L), alpha (ALPH) and animation are outside the
-// lossy block-transform path: ZW_EUNSUPPORTED.
+// (:938-993).  Lossless (VP8L) and animation are outside the lossy
+// block-transform path: ZW_EUNSUPPORTED, and so is alpha (ALPH) unless the
+// caller opts in with ZW_WEBP_ALPHA (zw_webp_parse_ex).
 // ---------------------------------------------------------------------------
 namespace {
 uint32_t rd32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
@@ -569,9 +570,11 @@ uint32_t rd24(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) 
 bool fourcc_is(const uint8_t* p, const char* s) { return memcmp(p, s, 4) == 0; }
 }  // namespace
 
-extern "C" int zw_webp_parse(const uint8_t* data, size_t len, zw_webp_info* info)
+// zw_webp_parse (flags 0) and zw_webp_parse_ex: with ZW_WEBP_ALPHA a VP8X file
+// with the alpha flag and a "VP8 " chunk parses, its first ALPH chunk recorded;
+// the flag without the chunk is ChunkMissing (read_image, decoder/api.rs:675-678).
+static int webp_parse_flags(const uint8_t* data, size_t len, int flags, zw_webp_info_ex* info)
 {
-    if (!info || (!data && len)) return ZW_EINVAL;
     memset(info, 0, sizeof *info);
     if (len < 8) return ZW_EBITSTREAM;
     if (!fourcc_is(data, "RIFF")) return ZW_ECHUNK_HEADER;  // ChunkHeaderInvalid(b"RIFF")
@@ -599,15 +602,15 @@ extern "C" int zw_webp_parse(const uint8_t* data, size_t len, zw_webp_info* info
         return ZW_EUNSUPPORTED;
     } else if (fourcc_is(ch, "VP8X")) {
         if (len < start + 10) return ZW_EBITSTREAM;
-        const uint8_t flags = data[start];
-        info->has_alpha = (flags & 0x10) != 0;
-        info->is_animated = (flags & 0x02) != 0;
+        const uint8_t chunk_flags = data[start];
+        info->has_alpha = (chunk_flags & 0x10) != 0;
+        info->is_animated = (chunk_flags & 0x02) != 0;
         info->width = rd24(data + start + 4) + 1;
         info->height = rd24(data + start + 7) + 1;
         if ((uint64_t)info->width * info->height > 0xffffffffull) return ZW_EIMAGE_TOO_LARGE;
         uint64_t pos = start + crounded;
         const uint64_t max_pos = pos + (riff_size > 12 ? riff_size - 12 : 0);
-        int have_vp8 = 0, have_vp8l = 0;
+        int have_vp8 = 0, have_vp8l = 0, have_alph = 0;
         while (pos < max_pos) {
             if (pos + 8 > len) break;  // read_chunk_header hits the end: BitStreamError -> stop scanning
             const uint8_t* c = data + pos;
@@ -618,16 +621,48 @@ extern "C" int zw_webp_parse(const uint8_t* data, size_t len, zw_webp_info* info
                 info->vp8_len = sz;
             } else if (fourcc_is(c, "VP8L")) {
                 have_vp8l = 1;
+            } else if (fourcc_is(c, "ALPH") && !have_alph) {
+                have_alph = 1;
+                info->alph_offset = pos + 8;
+                info->alph_len = sz;
             }
             pos += 8 + rsz;
         }
         info->is_lossy = have_vp8;
         info->is_lossless = have_vp8l && !have_vp8;
-        if (info->is_animated || have_vp8l || info->has_alpha) return ZW_EUNSUPPORTED;
+        const bool alpha_ok = (flags & ZW_WEBP_ALPHA) && have_vp8;
+        if (info->is_animated || have_vp8l || (info->has_alpha && !alpha_ok)) return ZW_EUNSUPPORTED;
         if (!have_vp8) return ZW_ECHUNK_MISSING;
+        if (info->has_alpha) {
+            if (!have_alph) return ZW_ECHUNK_MISSING;
+            if (info->alph_offset + info->alph_len > len) return ZW_EBITSTREAM;
+        }
     } else {
         return ZW_ECHUNK_HEADER;
     }
     if (info->vp8_offset + info->vp8_len > len) return ZW_EBITSTREAM;
     return ZW_OK;
+}
+
+extern "C" int zw_webp_parse_ex(const uint8_t* data, size_t len, int flags, zw_webp_info_ex* info)
+{
+    if (!info || (!data && len) || (flags & ~ZW_WEBP_ALPHA)) return ZW_EINVAL;
+    return webp_parse_flags(data, len, flags, info);
+}
+
+extern "C" int zw_webp_parse(const uint8_t* data, size_t len, zw_webp_info* info)
+{
+    if (!info || (!data && len)) return ZW_EINVAL;
+    zw_webp_info_ex e;
+    const int r = webp_parse_flags(data, len, 0, &e);
+    memset(info, 0, sizeof *info);
+    info->width = e.width;
+    info->height = e.height;
+    info->has_alpha = e.has_alpha;
+    info->is_lossy = e.is_lossy;
+    info->is_lossless = e.is_lossless;
+    info->is_animated = e.is_animated;
+    info->vp8_offset = e.vp8_offset;
+    info->vp8_len = e.vp8_len;
+    return r;
 }

@@ -92,6 +92,13 @@ extern "C" const char* zw_strerror(int code)
     case ZW_ECHUNK_MISSING: return "an expected chunk was missing";
     case ZW_EINCONSISTENT_SIZES: return "inconsistent image sizes";
     case ZW_EIMAGE_TOO_LARGE: return "image too large";
+    case ZW_EALPHA_PREPROCESSING: return "invalid alpha preprocessing";
+    case ZW_ECOMPRESSION_METHOD: return "invalid compression method";
+    case ZW_EHUFFMAN: return "invalid lossless Huffman code";
+    case ZW_ETRANSFORM: return "invalid lossless transform";
+    case ZW_ECOLOR_CACHE_BITS: return "invalid color cache bits";
+    case ZW_ELOSSLESS_SIGNATURE: return "invalid lossless signature";
+    case ZW_EVERSION_NUMBER: return "invalid lossless version number";
     default: return "unknown error";
     }
 }
@@ -366,6 +373,7 @@ static void ctx_release_decode(zw_ctx* c)
     if (c->tok_) (void)hipStreamSynchronize(c->tok_);
     c->tok_scratch.release();
     c->tok_recs.release();
+    c->alpha_tmp.release();
     for (PinBuf& p : c->pin) p.release();
 }
 

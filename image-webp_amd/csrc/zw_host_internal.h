@@ -66,6 +66,8 @@ enum DecPin {
     PIN_DOWNLOAD,    // planes / packed images down
     PIN_ERR_WORDS,   // the row-parallel kernels' sync / error words, the token parse's error words
     PIN_TOK_UPLOAD,  // the device token parse's upload (modes, probabilities, token partitions)
+    PIN_ALPHA0,      // the alpha decode's table and planes of a chunk, one per buffer set
+    PIN_ALPHA1,
     PIN_COUNT
 };
 
@@ -92,6 +94,10 @@ struct zw_ctx {
     };
     DecSet set[2];
     PinBuf pin[PIN_COUNT];
+    DevBuf alpha_tmp;    // zw_webp_decode_ex: the RGBA image on the device before its download
+    // the alpha work of the last alpha decode: [0] the ALPH payloads on the host
+    // threads (wall ms), [1] the filter kernels, [2] k_alpha_store (device ms)
+    float alpha_ms[3] = {0.f, 0.f, 0.f};
     DevBuf tok_scratch;  // the device token parse's upload, snapshots and offsets
     DevBuf tok_recs;     // the device token parse's records (sized by its count pass)
     uint64_t* tok_total = nullptr;  // pinned: the count pass's record bytes

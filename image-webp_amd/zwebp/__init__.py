@@ -61,6 +61,8 @@ _ERRS = {
     5: "Unsupported", 6: "OutOfMemory", 10: "Vp8MagicInvalid", 11: "ColorSpaceInvalid",
     12: "LumaPredictionModeInvalid", 13: "IntraPredictionModeInvalid", 14: "ChromaPredictionModeInvalid",
     15: "BitStreamError", 16: "UnsupportedFeature", 17: "NotEnoughInitData",
+    23: "InvalidAlphaPreprocessing", 24: "InvalidCompressionMethod", 25: "HuffmanError", 26: "TransformError",
+    27: "InvalidColorCacheBits", 28: "LosslessSignatureInvalid", 29: "VersionNumberInvalid",
 }
 
 
@@ -114,6 +116,13 @@ class _WebpInfo(ctypes.Structure):
     _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("has_alpha", ctypes.c_int),
                 ("is_lossy", ctypes.c_int), ("is_lossless", ctypes.c_int), ("is_animated", ctypes.c_int),
                 ("vp8_offset", ctypes.c_uint64), ("vp8_len", ctypes.c_uint64)]
+
+
+class _WebpInfoEx(ctypes.Structure):
+    _fields_ = _WebpInfo._fields_ + [("alph_offset", ctypes.c_uint64), ("alph_len", ctypes.c_uint64)]
+
+
+WEBP_ALPHA = 1  # ZW_WEBP_ALPHA
 
 
 class _DeviceImages(ctypes.Structure):
@@ -215,6 +224,15 @@ SIGNATURES = [
     ("zw_pipe_lanes", _I, [_VP]),
     ("zw_pipe_launch_frames", _I, [_VP]),
     ("zw_host_threads", _I, []),
+    ("zw_webp_parse_ex", _I, [_VP, _SZ, _I, ctypes.POINTER(_WebpInfoEx)]),
+    ("zw_webp_decode_batch_device", _I, [_VP, _I, ctypes.POINTER(_VP), ctypes.POINTER(_SZ), _I,
+                                         ctypes.POINTER(_DeviceImages), ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
+    ("zw_webp_decode_ex", _I, [_VP, _VP, _SZ, _I, _I, _I, ctypes.POINTER(_Bytes), ctypes.POINTER(_U32),
+                               ctypes.POINTER(_U32)]),
+    ("zw_alph_decode", _I, [_VP, _VP, _SZ, _U32, _U32, _VP]),
+    ("zw_dbg_alph_plane", _I, [_VP, _SZ, _U32, _U32, _VP, ctypes.POINTER(_I)]),
+    ("zw_dbg_vp8l_decode", _I, [_VP, _SZ, _VP, ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
+    ("zw_decode_alpha_times", _I, [_VP, ctypes.POINTER(ctypes.c_float)]),
 ]
 
 _LIB = None
@@ -669,7 +687,7 @@ def _vec4(v, default):
 
 def decode_batch_device_ptr(frames, ptr, capacity, width=None, height=None, channels=3, layout="chw", dtype="u8",
                             upsampling=UpsamplingMethod.Bilinear, scale=None, bias=None, frame_stride=None,
-                            plane_stride=None, row_stride=None, ctx=None):
+                            plane_stride=None, row_stride=None, ctx=None, _webp_flags=None):
     """zw_vp8_decode_batch_device, raw-pointer form: n VP8 key frames of one
     size into device memory at `ptr` (`capacity` elements of `dtype`), HWC
     (element i*frame_stride + y*row_stride + x*channels + c) or CHW
@@ -702,13 +720,17 @@ def decode_batch_device_ptr(frames, ptr, capacity, width=None, height=None, chan
     ptrs = (ctypes.c_void_p * n)(*[a.ctypes.data for a in arrs])
     lens = (ctypes.c_size_t * n)(*[a.size for a in arrs])
     w, h = ctypes.c_uint32(), ctypes.c_uint32()
+    if _webp_flags is not None:  # (whole WebP files: decode_webp_batch_device(alpha=True))
+        _check(L.zw_webp_decode_batch_device(c.handle, n, ptrs, lens, int(_webp_flags), ctypes.byref(out),
+                                             ctypes.byref(w), ctypes.byref(h)), "decode_webp_batch_device", DecodingError)
+        return w.value, h.value
     _check(L.zw_vp8_decode_batch_device(c.handle, n, ptrs, lens, ctypes.byref(out), ctypes.byref(w), ctypes.byref(h)),
            "decode_batch_device", DecodingError)
     return w.value, h.value
 
 
 def decode_batch_device(frames, out=None, channels=3, layout="chw", dtype="u8", upsampling=UpsamplingMethod.Bilinear,
-                        scale=None, bias=None, ctx=None):
+                        scale=None, bias=None, ctx=None, _webp=None):
     """n VP8 key frames of one size decoded straight into a torch tensor on the
     context's device, with no download, upload or host copy
     (zw_vp8_decode_batch_device; the values are decode_batch_device_ptr's).
@@ -737,6 +759,9 @@ def decode_batch_device(frames, out=None, channels=3, layout="chw", dtype="u8", 
     a0 = arrs[0]
     w = int(a0[6]) | ((int(a0[7]) & 0x3F) << 8) if a0.size >= 10 else 0
     h = int(a0[8]) | ((int(a0[9]) & 0x3F) << 8) if a0.size >= 10 else 0
+    webp_flags = None
+    if _webp is not None:  # (frames = the files' VP8 payloads, for the size; the call takes the files)
+        arrs, webp_flags = _webp
     tdt = {0: torch.uint8, 1: torch.float16, 2: torch.float32}
     dev = torch.device("cuda", c.device)
     if out is None:
@@ -769,21 +794,32 @@ def decode_batch_device(frames, out=None, channels=3, layout="chw", dtype="u8", 
     capacity = out.untyped_storage().nbytes() // out.element_size() - out.storage_offset()
     torch.cuda.current_stream(dev).synchronize()
     decode_batch_device_ptr(arrs, out.data_ptr(), capacity, w, h, ch, lay, dts[0], upsampling, scale, bias, fs, ps, rs,
-                            ctx=c)
+                            ctx=c, _webp_flags=webp_flags)
     return out
 
 
 def decode_webp_batch_device(files, out=None, channels=3, layout="chw", dtype="u8",
-                             upsampling=UpsamplingMethod.Bilinear, scale=None, bias=None, ctx=None):
+                             upsampling=UpsamplingMethod.Bilinear, scale=None, bias=None, ctx=None, alpha=False):
     """decode_batch_device over lossy WebP files: each RIFF container is
     stripped with webp_parse (vp8_offset / vp8_len).  ALPH, VP8L and animated
-    files raise DecodingError code 5, as webp_parse does."""
-    vp8 = []
+    files raise DecodingError code 5, as webp_parse does.
+
+    alpha=True (zw_webp_decode_batch_device with ZW_WEBP_ALPHA): files with an
+    ALPH chunk decode too; `channels` (or the tensor's) must be 4, and channel 3
+    holds each file's alpha (255 for a file without the alpha flag) by the same
+    store rule as the colours (u8 the byte; f32 a * scale[3] + bias[3]; f16 that
+    rounded to nearest even).  VP8L and animated files still raise code 5; a
+    file with the alpha flag but no ALPH chunk raises code 20."""
+    vp8, arrs = [], []
     for f in files:
         a = _as_u8(f)
-        info = webp_parse(a)
+        info = webp_parse(a, alpha=alpha)
+        arrs.append(a)
         vp8.append(a[info["vp8_offset"]:info["vp8_offset"] + info["vp8_len"]])
-    return decode_batch_device(vp8, out, channels, layout, dtype, upsampling, scale, bias, ctx)
+    if not alpha:
+        return decode_batch_device(vp8, out, channels, layout, dtype, upsampling, scale, bias, ctx)
+    return decode_batch_device(vp8, out, channels, layout, dtype, upsampling, scale, bias, ctx,
+                               _webp=(arrs, WEBP_ALPHA))
 
 
 def decode_batch_device_resized_ptr(frames, ptr, capacity, out_w, out_h, windows=None, channels=3, layout="chw",
@@ -1085,30 +1121,85 @@ def decode_rgb_kernel_ms(ctx=None):
     return float(ms.value)
 
 
-def webp_parse(data):
-    """WebPDecoder::new's container parse (decoder/api.rs:334-510): dict of the header facts."""
+def webp_parse(data, alpha=False):
+    """WebPDecoder::new's container parse (decoder/api.rs:334-510): dict of the header facts.
+    alpha=True (zw_webp_parse_ex with ZW_WEBP_ALPHA): a lossy file with the alpha
+    flag parses too, and the dict also holds alph_offset / alph_len."""
     L = load_library()
     a = _as_u8(data)
+    if alpha:
+        ex = _WebpInfoEx()
+        rc = L.zw_webp_parse_ex(_ptr(a) if a.size else None, a.size, WEBP_ALPHA, ctypes.byref(ex))
+        _check(rc, "WebPDecoder::new", DecodingError)
+        return {f: getattr(ex, f) for f, _ in _WebpInfoEx._fields_}
     info = _WebpInfo()
     rc = L.zw_webp_parse(_ptr(a) if a.size else None, a.size, ctypes.byref(info))
     _check(rc, "WebPDecoder::new", DecodingError)
     return {f: getattr(info, f) for f, _ in _WebpInfo._fields_}
 
 
-def _webp_decode(data, bpp, upsampling, ctx):
+def _webp_decode(data, bpp, upsampling, ctx, alpha=False):
     c = _ctx(ctx)
     L = c._lib
     a = _as_u8(data)
     out, w, h = _Bytes(), ctypes.c_uint32(), ctypes.c_uint32()
-    _check(L.zw_webp_decode(c.handle, _ptr(a) if a.size else None, a.size, bpp, upsampling, ctypes.byref(out),
-                            ctypes.byref(w), ctypes.byref(h)), "decode", DecodingError)
+    if alpha:
+        _check(L.zw_webp_decode_ex(c.handle, _ptr(a) if a.size else None, a.size, bpp, upsampling, WEBP_ALPHA,
+                                   ctypes.byref(out), ctypes.byref(w), ctypes.byref(h)), "decode", DecodingError)
+    else:
+        _check(L.zw_webp_decode(c.handle, _ptr(a) if a.size else None, a.size, bpp, upsampling, ctypes.byref(out),
+                                ctypes.byref(w), ctypes.byref(h)), "decode", DecodingError)
     return _take_image(L, out, w.value, h.value, bpp), w.value, h.value
 
 
-def decode_rgba(data, ctx=None):
-    """decode_rgba (decoder/api.rs:938): (flat RGBA bytes, width, height); lossy files."""
-    img, w, h = _webp_decode(data, 4, UpsamplingMethod.Bilinear, ctx)
+def decode_rgba(data, ctx=None, alpha=False):
+    """decode_rgba (decoder/api.rs:938): (flat RGBA bytes, width, height); lossy files.
+    alpha=True: a file with an ALPH chunk decodes with its alpha (zw_webp_decode_ex)."""
+    img, w, h = _webp_decode(data, 4, UpsamplingMethod.Bilinear, ctx, alpha)
     return img.reshape(-1), w, h
+
+
+def alph_decode(payload, width, height, ctx=None):
+    """zw_alph_decode: an ALPH chunk payload to the final (height, width) alpha
+    plane -- the host reader, then the device filter kernels."""
+    c = _ctx(ctx)
+    a = _as_u8(payload)
+    out = np.empty((int(height), int(width)), np.uint8)
+    _check(c._lib.zw_alph_decode(c.handle, _ptr(a) if a.size else None, a.size, int(width), int(height),
+                                 out.ctypes.data), "alph_decode", DecodingError)
+    return out
+
+
+def dbg_alph_plane(payload, width, height):
+    """zw_dbg_alph_plane (host only): ((height, width) plane before the filter is undone, filter 0..3)."""
+    L = load_library()
+    a = _as_u8(payload)
+    out = np.empty((int(height), int(width)), np.uint8)
+    flt = ctypes.c_int()
+    _check(L.zw_dbg_alph_plane(_ptr(a) if a.size else None, a.size, int(width), int(height), out.ctypes.data,
+                               ctypes.byref(flt)), "dbg_alph_plane", DecodingError)
+    return out, flt.value
+
+
+def dbg_vp8l_decode(data):
+    """zw_dbg_vp8l_decode (host only): a headered VP8L stream to a (height, width) uint32 array 0xAARRGGBB."""
+    L = load_library()
+    a = _as_u8(data)
+    w, h = ctypes.c_uint32(), ctypes.c_uint32()
+    p = _ptr(a) if a.size else None
+    _check(L.zw_dbg_vp8l_decode(p, a.size, None, ctypes.byref(w), ctypes.byref(h)), "dbg_vp8l_decode", DecodingError)
+    out = np.empty((h.value, w.value), np.uint32)
+    _check(L.zw_dbg_vp8l_decode(p, a.size, out.ctypes.data, ctypes.byref(w), ctypes.byref(h)), "dbg_vp8l_decode",
+           DecodingError)
+    return out
+
+
+def decode_alpha_times(ctx=None):
+    """zw_decode_alpha_times: (host ALPH ms, filter kernels ms, store kernel ms) of the last alpha decode."""
+    c = _ctx(ctx)
+    ms = (ctypes.c_float * 3)()
+    _check(c._lib.zw_decode_alpha_times(c.handle, ms), "decode_alpha_times")
+    return float(ms[0]), float(ms[1]), float(ms[2])
 
 
 def decode_rgb(data, ctx=None):
@@ -1121,10 +1212,11 @@ class WebPDecoder:
     """WebPDecoder (decoder/api.rs:306-906), lossy subset: new / dimensions / has_alpha /
     is_lossy / output_buffer_size / set_lossy_upsampling / read_image."""
 
-    def __init__(self, data, ctx=None):
+    def __init__(self, data, ctx=None, alpha=False):
         self._data = _as_u8(data)
         self._ctx = ctx
-        self._info = webp_parse(self._data)
+        self._alpha = bool(alpha)  # lossy files with an ALPH chunk open and decode to RGBA (api.rs:672-700)
+        self._info = webp_parse(self._data, alpha=self._alpha)
         self._up = UpsamplingMethod.Bilinear
 
     def dimensions(self):
@@ -1146,7 +1238,7 @@ class WebPDecoder:
     def read_image(self, buf=None):
         """Decodes into `buf` (a writable u8 buffer of output_buffer_size()) or returns a new array."""
         bpp = 4 if self.has_alpha() else 3
-        img, _, _ = _webp_decode(self._data, bpp, self._up, self._ctx)
+        img, _, _ = _webp_decode(self._data, bpp, self._up, self._ctx, self._alpha and bpp == 4)
         flat = img.reshape(-1)
         if buf is None:
             return flat

@@ -17,6 +17,9 @@
  *   zw_webp_parse           WebPDecoder::new (read_data)  src/decoder/api.rs:334-510
  *   zw_webp_decode          decode_rgb / decode_rgba   src/decoder/api.rs:938-993
  *   zw_webp_decode_into     decode_rgb_into / decode_rgba_into  src/decoder/api.rs:1004-1128
+ *   zw_webp_parse_ex / zw_webp_decode_ex / zw_webp_decode_batch_device (flag ZW_WEBP_ALPHA)
+ *                           read_image of a lossy file with alpha  src/decoder/api.rs:661-703,
+ *                           read_alpha_chunk / get_alpha_predictor  src/decoder/extended.rs:151-334
  *   zw_yuv_to_rgb           fill_rgb_buffer_fancy/_simple  src/decoder/yuv.rs:82 / :402
  *   zw_rgb_to_yuv420        convert_image_yuv/_y      src/decoder/yuv.rs:656 / :806
  *   zw_loop_filter_frame    filter_row_in_cache       src/decoder/vp8.rs:1172-1345
@@ -61,7 +64,15 @@ enum {
     ZW_EWEBP_SIGNATURE = 19,     /* WebpSignatureInvalid */
     ZW_ECHUNK_MISSING = 20,      /* ChunkMissing */
     ZW_EINCONSISTENT_SIZES = 21, /* InconsistentImageSizes */
-    ZW_EIMAGE_TOO_LARGE = 22     /* ImageTooLarge */
+    ZW_EIMAGE_TOO_LARGE = 22,    /* ImageTooLarge */
+    /* the ALPH chunk and the VP8L reader (decoder/extended.rs:273-334, decoder/lossless.rs) */
+    ZW_EALPHA_PREPROCESSING = 23, /* InvalidAlphaPreprocessing */
+    ZW_ECOMPRESSION_METHOD = 24,  /* InvalidCompressionMethod */
+    ZW_EHUFFMAN = 25,             /* HuffmanError */
+    ZW_ETRANSFORM = 26,           /* TransformError */
+    ZW_ECOLOR_CACHE_BITS = 27,    /* InvalidColorCacheBits */
+    ZW_ELOSSLESS_SIGNATURE = 28,  /* LosslessSignatureInvalid */
+    ZW_EVERSION_NUMBER = 29       /* VersionNumberInvalid */
 };
 
 /* UpsamplingMethod (decoder/api.rs:268-279), same order; Bilinear is the default. */
@@ -399,6 +410,66 @@ int zw_webp_decode(zw_ctx *ctx, const uint8_t *data, size_t len, int bpp, int up
  * of a lossy WebP file into out (out_len >= stride_bytes * height bytes). */
 int zw_webp_decode_into(zw_ctx *ctx, const uint8_t *data, size_t len, int bpp, int upsampling, uint8_t *out,
                         size_t out_len, uint32_t stride_bytes, uint32_t *width, uint32_t *height);
+/* ---- Lossy files with an alpha plane (new, opt-in) ----
+ * A VP8X file with the alpha flag carries an ALPH chunk beside its "VP8 " chunk
+ * (WebPDecoder::read_image, decoder/api.rs:661-703).  The entries above keep
+ * refusing such a file with ZW_EUNSUPPORTED; the entries below take
+ * flags = ZW_WEBP_ALPHA and decode it to RGBA with its true alpha.  The ALPH
+ * payload's entropy decoding (raw bytes, or a headerless VP8L stream whose
+ * green channel is the plane: read_alpha_chunk, decoder/extended.rs:273-334)
+ * runs on the host threads; the alpha filter is undone (get_alpha_predictor,
+ * extended.rs:151-211: out = predictor + residual mod 256) and channel 3 is
+ * written on the device.  Still VP8L images and animation stay ZW_EUNSUPPORTED. */
+enum { ZW_WEBP_ALPHA = 1 };
+typedef struct {
+    uint32_t width, height; /* canvas */
+    int has_alpha, is_lossy, is_lossless, is_animated;
+    uint64_t vp8_offset, vp8_len;   /* the "VP8 " chunk payload inside the file */
+    uint64_t alph_offset, alph_len; /* the first ALPH chunk's payload; 0, 0: none */
+} zw_webp_info_ex;
+/* zw_webp_parse with flags.  flags 0: zw_webp_parse's codes and fields (alph_*
+ * filled as far as the scan went).  ZW_WEBP_ALPHA: a VP8X file with the alpha
+ * flag and a "VP8 " chunk parses; the flag without an ALPH chunk is
+ * ZW_ECHUNK_MISSING (the reference, api.rs:675-678; libwebp would decode it as
+ * opaque).  Any other flag bit: ZW_EINVAL. */
+int zw_webp_parse_ex(const uint8_t *data, size_t len, int flags, zw_webp_info_ex *info);
+/* n whole WebP files of one size into the caller's device memory: the output,
+ * its addressing and every check are zw_vp8_decode_batch_device's, on the files'
+ * "VP8 " payloads (a container error returns its code before anything is
+ * queued).  flags 0: a file with alpha is ZW_EUNSUPPORTED.  ZW_WEBP_ALPHA:
+ * out->channels must be 4 (else ZW_EINVAL, before anything is queued); channel
+ * 3 of a file with alpha holds its alpha byte a by the store rule above (u8 a;
+ * f32 a * scale[3] + bias[3], rounded multiply then rounded add; f16 that float
+ * rounded to nearest even), of a file without the alpha flag 255.  The files'
+ * ALPH payloads are decoded on the host threads while the device decodes the
+ * colour planes; per chunk the planes are uploaded, the filter kernels run over
+ * the frames that use each filter, and k_alpha_store writes channel 3 after the
+ * colour conversion on the same stream.  An ALPH error returns its code. */
+int zw_webp_decode_batch_device(zw_ctx *ctx, int n, const uint8_t *const *files, const size_t *lens, int flags,
+                                const zw_device_images *out, uint32_t *width, uint32_t *height);
+/* zw_webp_decode with flags: one file to a packed host image through the same
+ * device path (a device temporary, then one download).  ZW_WEBP_ALPHA needs
+ * bpp 4 (else ZW_EINVAL). */
+int zw_webp_decode_ex(zw_ctx *ctx, const uint8_t *data, size_t len, int bpp, int upsampling, int flags, zw_bytes *out,
+                      uint32_t *width, uint32_t *height);
+/* One ALPH payload to the final alpha plane of a width x height image
+ * (plane_out: width * height bytes): the host reader, the device filter
+ * kernels, one download. */
+int zw_alph_decode(zw_ctx *ctx, const uint8_t *payload, size_t len, uint32_t width, uint32_t height,
+                   uint8_t *plane_out);
+/* Test hooks, host only (no device work).  zw_dbg_alph_plane: the plane before
+ * the filter is undone and *filter (0 none, 1 horizontal, 2 vertical, 3
+ * gradient).  zw_dbg_vp8l_decode: a headered VP8L stream (the "VP8L" chunk
+ * payload) to width * height pixels 0xAARRGGBB; argb_out == NULL reads only the
+ * header's dimensions. */
+int zw_dbg_alph_plane(const uint8_t *payload, size_t len, uint32_t width, uint32_t height, uint8_t *plane,
+                      int *filter);
+int zw_dbg_vp8l_decode(const uint8_t *data, size_t len, uint32_t *argb_out, uint32_t *width, uint32_t *height);
+/* The alpha work of the last alpha decode on ctx: ms[0] the ALPH payloads on
+ * the host threads (wall), ms[1] the filter kernels, ms[2] k_alpha_store
+ * (device time, summed over the chunks).  zw_decode_rgb_kernel_ms of such a
+ * call spans the colour conversion and the chunk's alpha upload and kernels. */
+int zw_decode_alpha_times(zw_ctx *ctx, float *ms);
 /* Device time (HIP events on the context stream) of the last decode batch:
  * ms[0] = k_dec_recon (dequant + iWHT/iDCT + prediction), ms[1] = k_loopfilter. */
 int zw_decode_kernel_times(zw_ctx *ctx, float *ms);
