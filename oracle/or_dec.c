@@ -542,6 +542,7 @@ void or_yuv_to_rgb_simple_c(const uint8_t *y, const uint8_t *u, const uint8_t *v
         for (size_t i = 0; i < (size_t)w * h; i++) out[i * 4 + 3] = 255;
 }
 size_t or_debug_struct_size(void) { return sizeof(or_enc_debug); }
+size_t or_census_struct_size(void) { return sizeof(or_i4_census); }
 /* all ten I4 predictions for a 13-pixel edge (L3,L2,L1,L0,P,A0..A7) */
 void or_i4_preds_edge_c(const uint8_t e[13], uint8_t out[160])
 {

@@ -795,6 +795,7 @@ typedef struct {
     benc_t hdr, parts[8], *part; /* token partitions; part = the current row's (mby % nparts) */
     int nparts;
     or_enc_debug *dbg;
+    or_i4_census *census;
     int pass;
 } enc_t;
 
@@ -992,6 +993,9 @@ static int pick_i4(const enc_t *e, int mbx, int mby, uint64_t i16_score, uint8_t
     int top_nz[4] = {0}, left_nz[4] = {0};
     int bidx[16] = {0};
     int maxm = e->method <= 3 ? 3 : (e->method == 4 ? 4 : 10);
+    /* census counters (or_encode_census only): the rate before the u16 cast */
+    or_i4_census *cen = (e->pass == 1 || e->pass == 2) ? e->census : NULL;
+    const int dp = e->pass - 1;
     for (int sby = 0; sby < 4; sby++)
         for (int sbx = 0; sbx < 4; sbx++) {
             int i = sby * 4 + sbx, y0 = sby * 4 + 1, x0 = sbx * 4 + 1;
@@ -1047,6 +1051,10 @@ static int pick_i4(const enc_t *e, int mbx, int mby, uint64_t i16_score, uint8_t
                 uint16_t mc = VP8_FIXED_COSTS_I4[tctx][lctx][m];
                 uint32_t rate = (uint32_t)mc + cc;
                 uint64_t sc = rd_score(sse, (uint16_t)rate, s->l_i4);
+                if (cen) {
+                    if (rate > cen->i4_rate_max[dp]) cen->i4_rate_max[dp] = rate;
+                    cen->i4_wrap_trials[dp] += rate > 65535;
+                }
                 if (sc < bscore) {
                     bscore = sc; bmode = m; bnz = hnz; memcpy(bq, q, sizeof q); bsse = sse; brate = rate;
                 }
@@ -1057,6 +1065,11 @@ static int pick_i4(const enc_t *e, int mbx, int mby, uint64_t i16_score, uint8_t
             left_nz[sby] = bnz;
             total_mode_cost += VP8_FIXED_COSTS_I4[tctx][lctx][bmode];
             running += rd_score(bsse, (uint16_t)brate, s->l_mode);
+            if (cen) {
+                cen->i4_wrap_winners[dp] += brate > 65535;
+                if (running >= i16_score) cen->i4_exit_score[dp]++;
+                else if (total_mode_cost > max_hdr) cen->i4_exit_hdr[dp]++;
+            }
             if (running >= i16_score) return 0;
             if (total_mode_cost > max_hdr) return 0;
             or_pred_b(ws, bmode, x0, y0, OR_BPS);
@@ -1661,6 +1674,14 @@ int or_encode(const uint8_t *data, size_t len, uint32_t width, uint32_t height, 
 int or_encode_parts(const uint8_t *data, size_t len, uint32_t width, uint32_t height, int color, int quality,
                     int method, int nparts, uint8_t **out, size_t *out_len, or_enc_debug *dbg)
 {
+    return or_encode_census(data, len, width, height, color, quality, method, nparts, out, out_len, dbg, NULL);
+}
+
+/* ... and the pick_best_intra4 census (zw_oracle.h or_i4_census), cleared first. */
+int or_encode_census(const uint8_t *data, size_t len, uint32_t width, uint32_t height, int color, int quality,
+                     int method, int nparts, uint8_t **out, size_t *out_len, or_enc_debug *dbg,
+                     or_i4_census *census)
+{
     *out = NULL;
     *out_len = 0;
     /* error order follows the reference: u16 dims (vp8.rs:3143), data length
@@ -1677,6 +1698,8 @@ int or_encode_parts(const uint8_t *data, size_t len, uint32_t width, uint32_t he
     memset(e, 0, sizeof E);
     e->nparts = nparts;
     e->dbg = dbg;
+    e->census = census;
+    if (census) memset(census, 0, sizeof *census);
     e->width = (int)width;
     e->height = (int)height;
     e->method = method > 6 ? 6 : method;

@@ -64,12 +64,28 @@ typedef struct {
                                            * left0, left1, then V), the zw_transform_quant_mbs record order */
 } or_enc_debug;
 
+/* pick_best_intra4 census, [0] pass 1, [1] pass 2.  The reference scores a
+ * candidate with `rate as u16` (vp8.rs:1979, :2005); these count the unwrapped
+ * rate (mode cost + coefficient cost).  A struct of its own, so that
+ * or_enc_debug keeps its layout for every binding written against it. */
+typedef struct {
+    uint32_t i4_rate_max[2];              /* largest unwrapped rate of any trial */
+    uint32_t i4_wrap_trials[2];           /* trials with rate > 65535 */
+    uint32_t i4_wrap_winners[2];          /* chosen sub-blocks whose rate > 65535 */
+    uint32_t i4_exit_score[2];            /* early exits: running >= i16_score */
+    uint32_t i4_exit_hdr[2];              /* early exits: total_mode_cost > max_hdr */
+} or_i4_census;
+
 /* encode_frame_lossy (encoder/vp8.rs:3132): raw VP8 frame bytes (malloc'd). */
 int or_encode(const uint8_t *data, size_t len, uint32_t width, uint32_t height, int color, int quality,
               int method, uint8_t **out, size_t *out_len, or_enc_debug *dbg);
 /* ... with nparts (1, 2, 4, 8) token partitions (vp8.rs:352-354, :1419-1421). */
 int or_encode_parts(const uint8_t *data, size_t len, uint32_t width, uint32_t height, int color, int quality,
                     int method, int nparts, uint8_t **out, size_t *out_len, or_enc_debug *dbg);
+/* ... filling *census (cleared first) as well; dbg and census may each be NULL. */
+int or_encode_census(const uint8_t *data, size_t len, uint32_t width, uint32_t height, int color, int quality,
+                     int method, int nparts, uint8_t **out, size_t *out_len, or_enc_debug *dbg,
+                     or_i4_census *census);
 void or_free(void *p);
 
 /* Vp8Decoder::decode_frame (decoder/vp8.rs:1526).  Planes are MB-aligned:
@@ -128,6 +144,7 @@ void or_quant_blocks_c(int n, const int32_t *coeffs, const uint8_t *ctx0, int ct
 uint32_t or_fixed_cost_i16(int mode);
 uint32_t or_fixed_cost_uv(int mode);
 size_t or_debug_struct_size(void);
+size_t or_census_struct_size(void);
 /* known-answer-test entry points (fast_math.rs, cost.rs, prediction.rs, bit_reader.rs) */
 float or_fm_roundf(float x);
 double or_fm_round(double x);

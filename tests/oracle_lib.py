@@ -33,6 +33,16 @@ class EncDebug(ctypes.Structure):
                 ("derr_in", ctypes.c_void_p)]
 
 
+class I4Census(ctypes.Structure):
+    # pick_best_intra4 census (or_i4_census), [pass 1, pass 2]: the rate before `as u16`
+    _fields_ = [("i4_rate_max", ctypes.c_uint32 * 2), ("i4_wrap_trials", ctypes.c_uint32 * 2),
+                ("i4_wrap_winners", ctypes.c_uint32 * 2), ("i4_exit_score", ctypes.c_uint32 * 2),
+                ("i4_exit_hdr", ctypes.c_uint32 * 2)]
+
+
+I4_CENSUS = tuple(n for n, _ in I4Census._fields_)
+
+
 class FrameHdr(ctypes.Structure):
     _fields_ = [("width", ctypes.c_int), ("height", ctypes.c_int), ("mbw", ctypes.c_int), ("mbh", ctypes.c_int),
                 ("filter_type", ctypes.c_int), ("filter_level", ctypes.c_int), ("sharpness", ctypes.c_int),
@@ -56,6 +66,8 @@ def lib():
                                 ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p]
         L.or_encode_parts.restype = ctypes.c_int
         L.or_encode_parts.argtypes = L.or_encode.argtypes[:7] + [ctypes.c_int] + L.or_encode.argtypes[7:]
+        L.or_encode_census.restype = ctypes.c_int
+        L.or_encode_census.argtypes = L.or_encode_parts.argtypes + [ctypes.c_void_p]
         L.or_decode.argtypes = [ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 8
         L.or_decode_header.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
         L.or_free.argtypes = [ctypes.c_void_p]
@@ -75,6 +87,8 @@ def lib():
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.or_debug_struct_size.restype = ctypes.c_size_t
         assert L.or_debug_struct_size() == ctypes.sizeof(EncDebug), "EncDebug layout mismatch"
+        L.or_census_struct_size.restype = ctypes.c_size_t
+        assert L.or_census_struct_size() == ctypes.sizeof(I4Census), "I4Census layout mismatch"
         _LIB = L
     return _LIB
 
@@ -138,8 +152,13 @@ def encode(img, w, h, color, quality=75, method=4, debug=False, nparts=1):
         dbg.p2_info = ctypes.addressof(p2)
         keep["p1_info"] = p1
         keep["p2_info"] = p2
-    rc = L.or_encode_parts(_p(img), img.size, w, h, color, quality, method, nparts, ctypes.byref(out),
-                           ctypes.byref(n), ctypes.byref(dbg) if dbg is not None else None)
+    if dbg is None:
+        rc = L.or_encode_parts(_p(img), img.size, w, h, color, quality, method, nparts, ctypes.byref(out),
+                               ctypes.byref(n), None)
+    else:
+        census = I4Census()
+        rc = L.or_encode_census(_p(img), img.size, w, h, color, quality, method, nparts, ctypes.byref(out),
+                                ctypes.byref(n), ctypes.byref(dbg), ctypes.byref(census))
     data = b""
     if rc == 0:
         data = ctypes.string_at(out.value, n.value)
@@ -152,6 +171,8 @@ def encode(img, w, h, color, quality=75, method=4, debug=False, nparts=1):
         keep["filter_level"] = dbg.filter_level
         keep["base_quant_index"] = dbg.base_quant_index
         keep["skip_prob"] = dbg.skip_prob
+        for k in I4_CENSUS:
+            keep[k] = list(getattr(census, k))
         return rc, data, keep
     return rc, data, None
 
