@@ -19,6 +19,7 @@
 
 #include "zw_enc_rows.h"
 #include "zw_enc_pairfinal.h"
+#include "zw_enc_i4pair.h"
 
 // Phase counters of the profiling build (tools/phase_prof.py names them).
 #define ZW_PH_N 28
@@ -1222,6 +1223,11 @@ __device__ bool pick_i4(const Ctx& C, unsigned long long i16_score, bool keep, u
 // (byte 2 hm + slot) in lanes 0..38.  Every per-MB decision (winners, early
 // exits, running scores) is the single search's, per MB: a search that ends
 // early leaves its lanes computing on, with their stores masked.
+// A step stays in the lanes from its values to the next step's contexts
+// (zw_enc_i4pair.h): the candidate modes come from a forward permute of the
+// ranks' inverse, every lane of an MB holds its MB's running state and takes
+// the step's winners into it, and only the two early exits are tested on the
+// scalar side, once per step.
 // ---------------------------------------------------------------------------
 struct I4PLane {
     uint32_t ix[4];  // bperm byte addresses (4 x V index) of the lane's pixels in rows 0..3, one per byte
@@ -1306,27 +1312,46 @@ DI uint32_t i4p_values(const Ctx& CA, const Ctx& CB, const int* x0, const int* y
     return l == 38 ? dcv : __builtin_amdgcn_perm(v[1], v[0], 0x06040200u);
 }
 
+// The running state of a paired search: in lane form every lane holds its MB's
+// (zw_enc_i4pair.h); in scalar form (ZW_I4P_LANES=0) the wave holds both MBs'.
+#if ZW_I4P_LANES
+typedef I4PState I4PSearch;
+#else
+struct I4PSearch {
+    I4State mb[2];
+};
+#endif
+
 template <int PASS, int NB>
 DI void i4p_step(const Ctx& CA, const Ctx& CB, const int* sbx, const int* sby, int K, const I4PLane& LC,
-                 I4State st[2], const bool act[2], bool keep)
+                 I4PSearch& st, const bool act[2], bool keep)
 {
     [[maybe_unused]] const Ctx& C = CA;  // (the phase counters)
     const int l = CA.lane, m = l & 15, hm = l >> 5;
     const int slot = NB == 2 ? (l >> 4) & 1 : 0;
     const int sl = NB == 2 ? 1 : 0;
+    int x0[NB], y0[NB];
+#pragma unroll
+    for (int h = 0; h < NB; h++) {
+        x0[h] = sbx[h] * 4 + 1;
+        y0[h] = sby[h] * 4 + 1;
+    }
+    const int bx = csel(slot, sbx[sl], sbx[0]), by = csel(slot, sby[sl], sby[0]);
+#if ZW_I4P_LANES
+    // the lane's block's contexts from its MB's state
+    const int tctx = i4p_tctx(st, bx, by), lctx = i4p_lctx(st, bx, by), ctx0 = i4p_nzctx(st, bx, by);
+#else
     // per (MB, slot) contexts, wave-uniform, then the lane's
-    int x0[NB], y0[NB], tc[2][NB], lc[2][NB], nc[2][NB];
+    int tc[2][NB], lc[2][NB], nc[2][NB];
 #pragma unroll
     for (int h = 0; h < NB; h++) {
         const int i = sby[h] * 4 + sbx[h];
-        x0[h] = sbx[h] * 4 + 1;
-        y0[h] = sby[h] * 4 + 1;
 #pragma unroll
         for (int mb = 0; mb < 2; mb++) {
-            tc[mb][h] = sby[h] == 0 ? 0 : (int)((st[mb].mpack >> (4 * (i - 4))) & 15);
-            lc[mb][h] = sbx[h] == 0 ? 0 : (int)((st[mb].mpack >> (4 * (i - 1))) & 15);
-            nc[mb][h] = (sby[h] == 0 ? 0 : (int)((st[mb].tnz >> sbx[h]) & 1)) +
-                        (sbx[h] == 0 ? 0 : (int)((st[mb].lnz >> sby[h]) & 1));
+            tc[mb][h] = sby[h] == 0 ? 0 : (int)((st.mb[mb].mpack >> (4 * (i - 4))) & 15);
+            lc[mb][h] = sbx[h] == 0 ? 0 : (int)((st.mb[mb].mpack >> (4 * (i - 1))) & 15);
+            nc[mb][h] = (sby[h] == 0 ? 0 : (int)((st.mb[mb].tnz >> sbx[h]) & 1)) +
+                        (sbx[h] == 0 ? 0 : (int)((st.mb[mb].lnz >> sby[h]) & 1));
         }
     }
     auto pick = [&](const int (&v)[2][NB]) {
@@ -1334,9 +1359,21 @@ DI void i4p_step(const Ctx& CA, const Ctx& CB, const int* sbx, const int* sby, i
         return csel(hm, b, a);
     };
     const int tctx = pick(tc), lctx = pick(lc), ctx0 = pick(nc);
-    const int bx = csel(slot, sbx[sl], sbx[0]), by = csel(slot, sby[sl], sby[0]);
+#endif
     const uint8_t* sYh = hm ? CB.sY : CA.sY;
     const LdsTables* Th = hm ? CB.T : CA.T;  // the lane's frame's tables (costs, probabilities)
+    const int k = (l >> 2) & 3, q = l & 3;
+    // what the candidate phase reads without knowing its mode: the costs of an
+    // empty block, its source row q, the mode costs' row
+    int hn[2];
+    uint32_t swq;
+    const uint16_t* fcrow;
+    auto read_ctx = [&]() {
+        hn[0] = (int)Th->binit[3][0][ctx0] & -(int)(ctx0 == 0);
+        hn[1] = (int)Th->beob[3][0][ctx0];
+        swq = *(const uint32_t*)(sYh + (by * 4 + q) * 16 + bx * 4);
+        fcrow = Th->fci4[tctx][lctx];
+    };
     PH_START();
     const uint32_t vp = i4p_values<NB>(CA, CB, x0, y0);
     // TrueMotion offsets V[5 + j] - V[4] of the lane's (MB, slot), as (x0, x1), (x3, x2) pairs
@@ -1354,6 +1391,9 @@ DI void i4p_step(const Ctx& CA, const Ctx& CB, const int* sbx, const int* sby, i
         ap32 = pack_lo(d3, d2);
     }
     PH_MARK_L(10, l, 0);
+#if ZW_I4P_INV
+    read_ctx();  // (before the ranking: its round trips hide these)
+#endif
     // ranking: the four rows of (MB, slot, mode) in one lane
     int pse = 0;
 #pragma unroll
@@ -1375,24 +1415,27 @@ DI void i4p_step(const Ctx& CA, const Ctx& CB, const int* sbx, const int* sby, i
     const int key = m < 10 ? (pse << 4) | m : 0x7fffffff;
     const int rank = rank16(key);
     PH_MARK_L(11, l, 0);
+#if ZW_I4P_INV
+    // candidate modes: the ranks of a group's modes are a permutation, so its
+    // inverse is one forward permute (lane (g, m) sends m to quad `rank` of its
+    // group) and a quad broadcast; nothing goes through the scalar unit
+    const int mv = i4p_mode(l, K, qb0(__builtin_amdgcn_ds_permute(4 * i4p_inv_dest(l, rank), m)));
+#else
     // candidate modes: k-th of each (MB, slot) group, four bits each, group g at bit 16 g
     unsigned long long modes = 0;
-    for (int k = 0; k < K; k++) {
-        const unsigned long long b = __ballot(m < 10 && rank == k);
+    for (int kk = 0; kk < K; kk++) {
+        const unsigned long long b = __ballot(m < 10 && rank == kk);
 #pragma unroll
         for (int g = 0; g < 4; g++)
-            modes |= (unsigned long long)__builtin_ctz((uint32_t)(b >> (16 * g)) | 0x10000u) << (16 * g + 4 * k);
+            modes |= (unsigned long long)__builtin_ctz((uint32_t)(b >> (16 * g)) | 0x10000u) << (16 * g + 4 * kk);
     }
-    const int k = (l >> 2) & 3, q = l & 3;
-    const int g = 2 * hm + slot;
-    const int mq = (int)((modes >> (16 * g + 4 * k)) & 15ull);
+    const int mq = (int)((modes >> (16 * (2 * hm + slot) + 4 * k)) & 15ull);
     const int mv = k < K ? mq : 0;  // (k >= K: a valid mode, never eligible)
-    const int mcost = Th->fci4[tctx][lctx][mv];
+    read_ctx();
+#endif
+    const int mcost = fcrow[mv];
     const uint32_t iq0 = LC.iq0, bs0 = LC.bs0, iq1 = LC.iq1, bs1 = LC.bs1;
     const int q0 = LC.q0, qa = LC.qa;
-    int hn[2];
-    hn[0] = (int)Th->binit[3][0][ctx0] & -(int)(ctx0 == 0);
-    hn[1] = (int)Th->beob[3][0][ctx0];
     uint32_t p01, p32;
     {
         const uint32_t iw = *(const uint32_t*)&Th->i4qa[mv][4 * q];
@@ -1405,12 +1448,8 @@ DI void i4p_step(const Ctx& CA, const Ctx& CB, const int* sbx, const int* sby, i
         p01 = tm ? clamp_pk(add_pk(q01, ap01)) : q01;
         p32 = tm ? clamp_pk(add_pk(q32, ap32)) : q32;
     }
-    uint32_t s01, s32;
-    {
-        const uint32_t sw = *(const uint32_t*)(sYh + (by * 4 + q) * 16 + bx * 4);
-        s01 = __builtin_amdgcn_perm(0u, sw, 0x0c010c00u);
-        s32 = __builtin_amdgcn_perm(0u, sw, 0x0c020c03u);
-    }
+    const uint32_t s01 = __builtin_amdgcn_perm(0u, swq, 0x0c010c00u);
+    const uint32_t s32 = __builtin_amdgcn_perm(0u, swq, 0x0c020c03u);
     PH_MARK_L(22, l, 0);
     const uint32_t R01 = sub_pk(s01, p01), R32 = sub_pk(s32, p32);
     int cf[4];
@@ -1441,6 +1480,41 @@ DI void i4p_step(const Ctx& CA, const Ctx& CB, const int* sbx, const int* sby, i
     const uint32_t score = (uint32_t)sse * 256u + (rate & 0xffffu) * LC.l_i4;
     const uint32_t key2 = k < K ? (score << 2) | (uint32_t)k : 0xffffffffu;
     const uint32_t kmin = min16u(key2);
+    const bool actl = hm ? act[1] : act[0];
+#if ZW_I4P_LANES
+    // the winner: the eligible quad holding its group's smallest key (k in the
+    // key's low bits: one quad).  Its words go to every lane of its MB, and every
+    // lane takes its MB's winners into its copy of the state.
+    const bool winl = key2 == kmin && k < K;
+    PH_MARK_L(12, l, 0);
+    {
+        const I4PWin own = i4p_win(rate, (uint32_t)mcost, last >= 0, (uint32_t)sse, mv);
+        uint32_t w0 = winl ? own.pk : 0u, w1 = winl ? own.sm : 0u;
+        w0 |= (uint32_t)ror8((int)w0);
+        w1 |= (uint32_t)ror8((int)w1);
+        w0 |= (uint32_t)ror4((int)w0);
+        w1 |= (uint32_t)ror4((int)w1);
+        const uint32_t lml = hm ? CB.S->l_mode : CA.S->l_mode;
+        if (NB == 2) {
+            // [h]: slot h's word in both rows of the MB
+            const auto p0 = __builtin_amdgcn_permlane16_swap(w0, w0, false, false);
+            const auto p1 = __builtin_amdgcn_permlane16_swap(w1, w1, false, false);
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                I4PWin w;
+                w.pk = p0[h];
+                w.sm = p1[h];
+                i4p_state_update(st, sbx[h], sby[h], w, lml);
+            }
+        } else {
+            I4PWin w;
+            w.pk = w0;
+            w.sm = w1;
+            i4p_state_update(st, sbx[0], sby[0], w, lml);
+        }
+        if (actl && m == 0 && ((l >> 4) & 1) < NB) (hm ? CB.M : CA.M)->modes[by * 4 + bx] = (uint8_t)(w1 >> 24);
+    }
+#else
     const unsigned long long win = __ballot(key2 == kmin);
     // the winner's u16 rate, mode cost (< 2^15) and nonzero flag in one word: one
     // readlane for them instead of three
@@ -1454,14 +1528,18 @@ DI void i4p_step(const Ctx& CA, const Ctx& CB, const int* sbx, const int* sby, i
         for (int h = 0; h < NB; h++) {
             const int gg = 2 * mb + h;
             const int bk = __builtin_ctz((uint32_t)(win >> (16 * gg)) & 0xffffu) >> 2;
-            const int bmode = (int)((modes >> (16 * gg + 4 * bk)) & 15ull);
             const int wl = 16 * gg + 4 * bk;
+#if ZW_I4P_INV
+            const int bmode = __builtin_amdgcn_readlane(mv, wl);
+#else
+            const int bmode = (int)((modes >> (16 * gg + 4 * bk)) & 15ull);
+#endif
             const uint32_t bsse = (uint32_t)__builtin_amdgcn_readlane(sse, wl);
             const uint32_t bpk = (uint32_t)__builtin_amdgcn_readlane((int)pk, wl);
             const uint32_t brate = bpk & 0xffffu;
             const int bnz = (int)(bpk >> 31);
             const int i = sby[h] * 4 + sbx[h];
-            I4State& s = st[mb];
+            I4State& s = st.mb[mb];
             s.tnz = (s.tnz & ~(1u << sbx[h])) | ((uint32_t)bnz << sbx[h]);
             s.lnz = (s.lnz & ~(1u << sby[h])) | ((uint32_t)bnz << sby[h]);
             s.nzm |= (uint32_t)bnz << i;
@@ -1471,9 +1549,10 @@ DI void i4p_step(const Ctx& CA, const Ctx& CB, const int* sbx, const int* sby, i
             if (act[mb] && l == gg) M->modes[i] = (uint8_t)bmode;
         }
     }
+    const bool winl = k == (__builtin_ctz((uint32_t)(win >> (16 * (2 * hm + slot))) & 0xffffu) >> 2);
+#endif
     // the winners' quads write their rows of the reconstruction (and levels)
-    const int bks = __builtin_ctz((uint32_t)(win >> (16 * g)) & 0xffffu) >> 2;
-    if (k == bks && ((l >> 4) & 1) < NB && (hm ? act[1] : act[0])) {
+    if (winl && ((l >> 4) & 1) < NB && actl) {
         MbLds* M = hm ? CB.M : CA.M;
         const int xo = csel(slot, x0[sl], x0[0]), yo = csel(slot, y0[sl], y0[0]);
         const uint32_t wd = __builtin_amdgcn_perm(r32, r01, 0x04060200u);
@@ -1499,17 +1578,21 @@ __device__ uint32_t pick_i4_pair(const Ctx& CA, const Ctx& CB, unsigned long lon
                                  bool actA, bool actB, bool keep, uint32_t& nzA, uint32_t& nzB)
 {
     const int K = CA.method <= 3 ? 3 : 4;
-    I4State st[2];
-    st[0].running = 211ull * CA.S->l_mode;
-    st[1].running = 211ull * CB.S->l_mode;
+    I4PSearch st;
+#if ZW_I4P_LANES
+    i4p_state_init(st, (CA.lane >> 5) ? CB.S->l_mode : CA.S->l_mode);
+#else
+    st.mb[0].running = 211ull * CA.S->l_mode;
+    st.mb[1].running = 211ull * CB.S->l_mode;
 #pragma unroll
     for (int mb = 0; mb < 2; mb++) {
-        st[mb].total_mc = 0;
-        st[mb].mpack = 0;
-        st[mb].tnz = st[mb].lnz = st[mb].nzm = 0;
+        st.mb[mb].total_mc = 0;
+        st.mb[mb].mpack = 0;
+        st.mb[mb].tnz = st.mb[mb].lnz = st.mb[mb].nzm = 0;
     }
-    bool act[2] = {actA, actB};  // (an MB without a search: its lanes run masked)
     const unsigned long long lim[2] = {i16A, i16B};
+#endif
+    bool act[2] = {actA, actB};  // (an MB without a search: its lanes run masked)
     I4PLane LC;
     i4p_lane_init(CA, CB, LC);
     for (int s = 0; s < 10; s++) {
@@ -1521,13 +1604,24 @@ __device__ uint32_t pick_i4_pair(const Ctx& CA, const Ctx& CB, unsigned long lon
         } else {
             i4p_step<PASS, 1>(CA, CB, &sbxA, &sbyA, K, LC, st, act, keep);
         }
+#if ZW_I4P_LANES
+        // the one way out of the lanes per step: each MB's exits, from its first lane
+        if (__ballot(i4p_exit(st, i16A)) & 1ull) act[0] = false;
+        if ((__ballot(i4p_exit(st, i16B)) >> 32) & 1ull) act[1] = false;
+#else
 #pragma unroll
         for (int mb = 0; mb < 2; mb++)
-            if (st[mb].running >= lim[mb] || st[mb].total_mc > 256u * 16u * 16u / 4u) act[mb] = false;
+            if (st.mb[mb].running >= lim[mb] || st.mb[mb].total_mc > 256u * 16u * 16u / 4u) act[mb] = false;
+#endif
         if (!act[0] && !act[1]) return 0;
     }
-    nzA = st[0].nzm;
-    nzB = st[1].nzm;
+#if ZW_I4P_LANES
+    nzA = (uint32_t)__builtin_amdgcn_readlane((int)st.nzt, 0) & 0xffffu;
+    nzB = (uint32_t)__builtin_amdgcn_readlane((int)st.nzt, 32) & 0xffffu;
+#else
+    nzA = st.mb[0].nzm;
+    nzB = st.mb[1].nzm;
+#endif
     return (uint32_t)act[0] | ((uint32_t)act[1] << 1);
 }
 
