@@ -129,6 +129,41 @@ struct ZwAlphaFrame {
     uint32_t has_alpha, filter, plane, pad;
 };
 
+// The lossless kernels' per-frame table entry (zw_vp8l_kernels.hip).  s[k] is
+// the k-th inverse step (the bitstream's transforms in reverse order): type 0
+// predictor, 1 cross-colour, 2 subtract-green, 3 colour indexing; bits =
+// size_bits (types 0, 1) or table_size (type 3); off = where the step's
+// sub-image or table starts in the frame's data region (bytes, 16-aligned).
+// tw = the coded image's width; index_step = the step that is the colour
+// indexing inverse (ZW_LL_NO_INDEX: none): steps before it work the coded
+// buffer at width tw, it expands into the frame's full-width buffer, and the
+// steps after it (and the store) work that one at the canvas width.
+#define ZW_LL_NO_INDEX 0xffffffffu
+struct ZwLlStep {
+    uint32_t type, bits, off, pad;
+};
+struct ZwLlFrame {
+    uint32_t tw, has_alpha, nsteps, index_step;
+    ZwLlStep s[4];
+};
+// A chunk of frames on the device: frame f's slot at slots + f * sstride holds
+// its coded image (w * h words of room, 16 bytes of slack) and, doff bytes in,
+// its transform data; its full-width buffer is at full + f * bstride.
+// Where a run of lossless frames goes: the caller's tensor as zwk_ll_store takes it.
+struct ZwLlOut {
+    int layout, dtype, channels;
+    uint8_t* data;  // the run's first frame
+    size_t elsize;
+    ZwY2rDev P;
+};
+struct ZwLlChunk {
+    uint8_t* slots;
+    uint8_t* full;
+    const ZwLlFrame* tab;
+    size_t sstride, doff, bstride;
+    int w, h;
+};
+
 // k_yuv2rgb_resize's per-frame table entry (zw_vp8_decode_batch_device_resized):
 // the frame's slot in the caller's batch and its source window in frame pixels.
 struct ZwResizeFrame {

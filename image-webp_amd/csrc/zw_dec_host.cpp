@@ -17,6 +17,7 @@
 #include <memory>
 #include <mutex>
 #include <unordered_map>
+#include <utility>
 #include <new>
 #include <string>
 #include <vector>
@@ -66,6 +67,9 @@ hipError_t zwk_alpha_unfilter(hipStream_t s, uint8_t* planes, size_t pstride, in
 hipError_t zwk_alpha_store(hipStream_t s, const uint8_t* planes, size_t pstride, const ZwAlphaFrame* tab, int w, int h,
                            int layout, int dtype, void* out, const ZwY2rDev* P, int nframes);
 }
+// zw_vp8l_host.cpp: a run of lossless files into the caller's tensor
+int zw_ll_decode_run(zw_ctx* ctx, int n, const uint8_t* const* payload, const size_t* plen, const uint8_t* has_alpha,
+                     uint32_t w, uint32_t h, const ZwLlOut& O);
 #include "zw_tokl.h"
 
 using namespace zwdec;
@@ -1486,18 +1490,35 @@ extern "C" int zw_vp8_decode_batch_device(zw_ctx* ctx, int n, const uint8_t* con
 extern "C" int zw_webp_decode_batch_device(zw_ctx* ctx, int n, const uint8_t* const* files, const size_t* lens,
                                            int flags, const zw_device_images* out, uint32_t* width, uint32_t* height)
 {
-    if (!ctx || n <= 0 || !files || !lens || !out || !out->data || (flags & ~ZW_WEBP_ALPHA)) return ZW_EINVAL;
+    if (!ctx || n <= 0 || !files || !lens || !out || !out->data || (flags & ~(ZW_WEBP_ALPHA | ZW_WEBP_LOSSLESS)))
+        return ZW_EINVAL;
     if (!device_format_ok(out)) return ZW_EINVAL;
     const bool alpha = (flags & ZW_WEBP_ALPHA) != 0;
     if (alpha && out->channels != 4) return ZW_EINVAL;
     std::vector<const uint8_t*> vp8((size_t)n), alph((size_t)n, nullptr);
     std::vector<size_t> vlen((size_t)n), alen((size_t)n, 0);
+    std::vector<uint8_t> lossless((size_t)n, 0), ll_alpha((size_t)n, 0);
+    std::vector<std::pair<uint32_t, uint32_t>> dims((size_t)n);  // each file's canvas
+    uint32_t cw = 0, chh = 0;
+    bool any_lossless = false;
     for (int i = 0; i < n; i++) {
         if (!files[i] && lens[i]) return ZW_EINVAL;
         zw_webp_info_ex info;
         if (int r = zw_webp_parse_ex(files[i], lens[i], flags, &info)) return r;
         vp8[i] = files[i] + info.vp8_offset;
         vlen[i] = (size_t)info.vp8_len;
+        dims[i] = {info.width, info.height};
+        if (i == 0) cw = info.width, chh = info.height;
+        if (info.is_lossless) {
+            // read_image: the VP8L header against the canvas (decode_frame, decoder/lossless.rs:103-118)
+            uint32_t lw = 0, lh = 0;
+            if (int r = zwvp8l::read_header(vp8[i], vlen[i], &lw, &lh)) return r;
+            if (lw != info.width || lh != info.height) return ZW_EINCONSISTENT_SIZES;
+            lossless[i] = 1;
+            ll_alpha[i] = info.has_alpha != 0;
+            any_lossless = true;
+            continue;
+        }
         int fw = 0, fh = 0;  // read_image: InconsistentImageSizes (decoder/api.rs:668-670)
         if (peek_dims(vp8[i], vlen[i], &fw, &fh) && ((uint32_t)fw != info.width || (uint32_t)fh != info.height))
             return ZW_EINCONSISTENT_SIZES;
@@ -1506,20 +1527,60 @@ extern "C" int zw_webp_decode_batch_device(zw_ctx* ctx, int n, const uint8_t* co
             alen[i] = (size_t)info.alph_len;
         }
     }
-    return device_batch(ctx, n, vp8.data(), vlen.data(), out, width, height, alpha ? alph.data() : nullptr,
-                        alpha ? alen.data() : nullptr);
+    if (!any_lossless)
+        return device_batch(ctx, n, vp8.data(), vlen.data(), out, width, height, alpha ? alph.data() : nullptr,
+                            alpha ? alen.data() : nullptr);
+    // A batch with lossless files: one size (the first file's canvas), checked
+    // with the whole tensor before anything is queued; then maximal runs of one
+    // kind, each a pass of its own at the run's frame offset.
+    for (int i = 1; i < n; i++)
+        if (dims[i].first != cw || dims[i].second != chh) return ZW_EINVAL;
+    if (cw == 0 || chh == 0 || cw > 16384 || chh > 16384) return ZW_EINVALID_DIMENSIONS;
+    size_t elsize = 0;
+    if (int r = check_device_extent(ctx, out, (size_t)n, cw, chh, &elsize)) return r;
+    ctx->ll_ms[0] = ctx->ll_ms[1] = ctx->ll_ms[2] = 0.f;
+    for (int a = 0; a < n;) {
+        int b = a + 1;
+        while (b < n && lossless[b] == lossless[a]) b++;
+        zw_device_images sub = *out;
+        sub.data = (uint8_t*)out->data + (size_t)a * out->frame_stride * elsize;
+        sub.capacity = out->capacity - (size_t)a * out->frame_stride;
+        if (lossless[a]) {
+            ZwLlOut O;
+            O.layout = out->layout;
+            O.dtype = out->dtype;
+            O.channels = out->channels;
+            O.data = (uint8_t*)sub.data;
+            O.elsize = elsize;
+            O.P = device_strides(out);
+            if (int r = zw_ll_decode_run(ctx, b - a, vp8.data() + a, vlen.data() + a, ll_alpha.data() + a, cw, chh, O))
+                return r;
+        } else {
+            uint32_t rw = 0, rh = 0;
+            if (int r = device_batch(ctx, b - a, vp8.data() + a, vlen.data() + a, &sub, &rw, &rh,
+                                     alpha ? alph.data() + a : nullptr, alpha ? alen.data() + a : nullptr))
+                return r;
+            if (rw != cw || rh != chh) return ZW_EINVAL;
+        }
+        a = b;
+    }
+    if (width) *width = cw;
+    if (height) *height = chh;
+    return ZW_OK;
 }
 
 extern "C" int zw_webp_decode_ex(zw_ctx* ctx, const uint8_t* data, size_t len, int bpp, int upsampling, int flags,
                                  zw_bytes* out, uint32_t* width, uint32_t* height)
 {
     if (flags == 0) return zw_webp_decode(ctx, data, len, bpp, upsampling, out, width, height);
-    if (!ctx || !out || flags != ZW_WEBP_ALPHA || bpp != 4 || (!data && len)) return ZW_EINVAL;
+    if (!ctx || !out || (flags & ~(ZW_WEBP_ALPHA | ZW_WEBP_LOSSLESS)) || (bpp != 3 && bpp != 4) || (!data && len))
+        return ZW_EINVAL;
+    if ((flags & ZW_WEBP_ALPHA) && bpp != 4) return ZW_EINVAL;
     out->data = nullptr;
     out->len = 0;
     zw_webp_info_ex info;
     if (int r = zw_webp_parse_ex(data, len, flags, &info)) return r;
-    const size_t fbytes = (size_t)info.width * info.height * 4;
+    const size_t fbytes = (size_t)info.width * info.height * (size_t)bpp;
     HIPOK(hipSetDevice(ctx->device));
     void* d = ctx->alpha_tmp.reserve(fbytes);
     if (!d) return ZW_ENOMEM;
@@ -1529,10 +1590,10 @@ extern "C" int zw_webp_decode_ex(zw_ctx* ctx, const uint8_t* data, size_t len, i
     img.capacity = fbytes;
     img.layout = ZW_LAYOUT_HWC;
     img.dtype = ZW_DTYPE_U8;
-    img.channels = 4;
+    img.channels = bpp;
     img.upsampling = upsampling;
     img.frame_stride = fbytes;
-    img.row_stride = (size_t)info.width * 4;
+    img.row_stride = (size_t)info.width * (size_t)bpp;
     const uint8_t* f[1] = {data};
     const size_t l[1] = {len};
     uint32_t w = 0, h = 0;

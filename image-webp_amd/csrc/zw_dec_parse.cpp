@@ -562,7 +562,8 @@ extern "C" int zw_dbg_tokl_frame(const uint8_t* vp8, size_t len, int* match)
 // is a VP8 chunk, then read_image (:640-700) + decode_rgb / decode_rgba
 // (:938-993).  Lossless (VP8L) and animation are outside the lossy
 // block-transform path: ZW_EUNSUPPORTED, and so is alpha (ALPH) unless the
-// caller opts in with ZW_WEBP_ALPHA (zw_webp_parse_ex).
+// caller opts in with ZW_WEBP_ALPHA (zw_webp_parse_ex); a still VP8L image
+// parses with ZW_WEBP_LOSSLESS.
 // ---------------------------------------------------------------------------
 namespace {
 uint32_t rd32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
@@ -570,9 +571,26 @@ uint32_t rd24(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) 
 bool fourcc_is(const uint8_t* p, const char* s) { return memcmp(p, s, 4) == 0; }
 }  // namespace
 
+// The first five bytes of a VP8L payload (decoder/api.rs:378-395): the signature
+// byte, 14 + 14 bits of size, the alpha bit (bit 28 of the four bytes after the
+// signature) and a 3-bit version that must be 0.
+static int vp8l_header(const uint8_t* p, uint64_t avail, uint32_t* w, uint32_t* h, int* alpha)
+{
+    if (avail < 5) return ZW_EBITSTREAM;
+    if (p[0] != 0x2f) return ZW_ELOSSLESS_SIGNATURE;
+    const uint32_t v = rd32(p + 1);
+    if (v >> 29) return ZW_EVERSION_NUMBER;
+    *w = (v & 0x3fff) + 1;
+    *h = ((v >> 14) & 0x3fff) + 1;
+    *alpha = (int)((v >> 28) & 1u);
+    return ZW_OK;
+}
+
 // zw_webp_parse (flags 0) and zw_webp_parse_ex: with ZW_WEBP_ALPHA a VP8X file
 // with the alpha flag and a "VP8 " chunk parses, its first ALPH chunk recorded;
 // the flag without the chunk is ChunkMissing (read_image, decoder/api.rs:675-678).
+// With ZW_WEBP_LOSSLESS a simple "VP8L" file and a VP8X file whose image is a
+// "VP8L" chunk parse, vp8_offset / vp8_len giving that chunk's payload.
 static int webp_parse_flags(const uint8_t* data, size_t len, int flags, zw_webp_info_ex* info)
 {
     memset(info, 0, sizeof *info);
@@ -599,7 +617,10 @@ static int webp_parse_flags(const uint8_t* data, size_t len, int flags, zw_webp_
         info->vp8_len = csize;
     } else if (fourcc_is(ch, "VP8L")) {
         info->is_lossless = 1;
-        return ZW_EUNSUPPORTED;
+        if (!(flags & ZW_WEBP_LOSSLESS)) return ZW_EUNSUPPORTED;
+        if (int r = vp8l_header(data + start, len - start, &info->width, &info->height, &info->has_alpha)) return r;
+        info->vp8_offset = start;
+        info->vp8_len = csize;
     } else if (fourcc_is(ch, "VP8X")) {
         if (len < start + 10) return ZW_EBITSTREAM;
         const uint8_t chunk_flags = data[start];
@@ -611,6 +632,7 @@ static int webp_parse_flags(const uint8_t* data, size_t len, int flags, zw_webp_
         uint64_t pos = start + crounded;
         const uint64_t max_pos = pos + (riff_size > 12 ? riff_size - 12 : 0);
         int have_vp8 = 0, have_vp8l = 0, have_alph = 0;
+        uint64_t vp8l_off = 0, vp8l_len = 0;
         while (pos < max_pos) {
             if (pos + 8 > len) break;  // read_chunk_header hits the end: BitStreamError -> stop scanning
             const uint8_t* c = data + pos;
@@ -620,6 +642,10 @@ static int webp_parse_flags(const uint8_t* data, size_t len, int flags, zw_webp_
                 info->vp8_offset = pos + 8;
                 info->vp8_len = sz;
             } else if (fourcc_is(c, "VP8L")) {
+                if (!have_vp8l && !have_vp8) {
+                    vp8l_off = pos + 8;
+                    vp8l_len = sz;
+                }
                 have_vp8l = 1;
             } else if (fourcc_is(c, "ALPH") && !have_alph) {
                 have_alph = 1;
@@ -630,6 +656,16 @@ static int webp_parse_flags(const uint8_t* data, size_t len, int flags, zw_webp_
         }
         info->is_lossy = have_vp8;
         info->is_lossless = have_vp8l && !have_vp8;
+        if ((flags & ZW_WEBP_LOSSLESS) && info->is_lossless && !info->is_animated) {
+            // the image is the VP8L chunk (read_image, decoder/api.rs:648-660); has_alpha stays the VP8X flag
+            if (vp8l_off + vp8l_len > len) return ZW_EBITSTREAM;
+            uint32_t lw = 0, lh = 0;
+            int la = 0;
+            if (int r = vp8l_header(data + vp8l_off, vp8l_len, &lw, &lh, &la)) return r;
+            info->vp8_offset = vp8l_off;
+            info->vp8_len = vp8l_len;
+            return ZW_OK;
+        }
         const bool alpha_ok = (flags & ZW_WEBP_ALPHA) && have_vp8;
         if (info->is_animated || have_vp8l || (info->has_alpha && !alpha_ok)) return ZW_EUNSUPPORTED;
         if (!have_vp8) return ZW_ECHUNK_MISSING;
@@ -646,7 +682,7 @@ static int webp_parse_flags(const uint8_t* data, size_t len, int flags, zw_webp_
 
 extern "C" int zw_webp_parse_ex(const uint8_t* data, size_t len, int flags, zw_webp_info_ex* info)
 {
-    if (!info || (!data && len) || (flags & ~ZW_WEBP_ALPHA)) return ZW_EINVAL;
+    if (!info || (!data && len) || (flags & ~(ZW_WEBP_ALPHA | ZW_WEBP_LOSSLESS))) return ZW_EINVAL;
     return webp_parse_flags(data, len, flags, info);
 }
 

@@ -68,6 +68,8 @@ enum DecPin {
     PIN_TOK_UPLOAD,  // the device token parse's upload (modes, probabilities, token partitions)
     PIN_ALPHA0,      // the alpha decode's table and planes of a chunk, one per buffer set
     PIN_ALPHA1,
+    PIN_VP8L0,       // the lossless decode's table, coded images and transform data of a chunk, one per staging set
+    PIN_VP8L1,
     PIN_COUNT
 };
 
@@ -98,6 +100,9 @@ struct zw_ctx {
     // the alpha work of the last alpha decode: [0] the ALPH payloads on the host
     // threads (wall ms), [1] the filter kernels, [2] k_alpha_store (device ms)
     float alpha_ms[3] = {0.f, 0.f, 0.f};
+    // the last lossless decode: [0] the VP8L entropy decode on the host threads
+    // (wall ms), [1] the transform kernels, [2] the store kernel (device ms)
+    float ll_ms[3] = {0.f, 0.f, 0.f};
     DevBuf tok_scratch;  // the device token parse's upload, snapshots and offsets
     DevBuf tok_recs;     // the device token parse's records (sized by its count pass)
     uint64_t* tok_total = nullptr;  // pinned: the count pass's record bytes

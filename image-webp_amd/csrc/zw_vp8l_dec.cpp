@@ -9,6 +9,7 @@
 // of at most 16384.  A failed allocation is ZW_ENOMEM.
 #include "zw_vp8l_dec.h"
 
+#include <cstdlib>
 #include <cstring>
 #include <new>
 
@@ -594,8 +595,19 @@ int header(BitReader& br, uint32_t* w, uint32_t* h)
     return ZW_OK;
 }
 
-int decode_frame_impl(const uint8_t* data, size_t len, uint32_t width, uint32_t height, bool implicit_dims,
-                      std::vector<uint8_t>& rgba, std::vector<uint8_t>* transforms)
+}  // namespace
+
+int read_header(const uint8_t* data, size_t len, uint32_t* width, uint32_t* height)
+{
+    BitReader br(data, len);
+    return header(br, width, height);
+}
+
+namespace {
+
+// px == NULL: `grow` is sized to the image once the transforms have been read
+int decode_coded_impl(const uint8_t* data, size_t len, uint32_t width, uint32_t height, bool implicit_dims, uint8_t* px,
+                      size_t cap, std::vector<uint8_t>* grow, Coded& out)
 {
     Decoder D(data, len);
     if (implicit_dims) {
@@ -606,39 +618,104 @@ int decode_frame_impl(const uint8_t* data, size_t len, uint32_t width, uint32_t 
         if ((width || height) && (D.width != width || D.height != height)) return ZW_EINCONSISTENT_SIZES;
     }
     if (D.width == 0 || D.height == 0 || D.width > 16384 || D.height > 16384) return ZW_EINVALID_DIMENSIONS;
+    out.width = D.width;
+    out.height = D.height;
+    out.tf.clear();
     uint32_t tw = 0;
     const int rt = D.read_transforms(&tw);
-    if (transforms) *transforms = D.order;
+    out.tw = tw;
+    for (uint8_t type : D.order) {
+        CodedTransform t;
+        t.type = type;
+        t.bits = type == T_COLOR_INDEXING ? D.tf[type].table_size : D.tf[type].size_bits;
+        t.data.swap(D.tf[type].data);
+        out.tf.push_back(std::move(t));
+    }
     if (rt) return rt;
-    rgba.assign((size_t)D.width * D.height * 4, 0);  // (tw <= width: the coded image fits)
-    if (int r = D.decode_image_stream(tw, D.height, true, rgba.data())) return r;
-    uint32_t w = tw;
-    for (size_t k = D.order.size(); k-- > 0;) {
-        const Transform& T = D.tf[D.order[k]];
-        switch (D.order[k]) {
-        case T_PREDICTOR: inverse_predictor(rgba.data(), w, D.height, T.size_bits, T.data.data()); break;
-        case T_COLOR: inverse_color(rgba.data(), w, D.height, T.size_bits, T.data.data()); break;
+    if (!px) {
+        grow->assign((size_t)D.width * D.height * 4, 0);
+        px = grow->data();
+    } else if (cap < (size_t)D.width * D.height * 4) {  // (tw <= width: the coded image fits)
+        return ZW_EINVAL;
+    }
+    return D.decode_image_stream(tw, D.height, true, px);
+}
+
+}  // namespace
+
+uint32_t packed_width(uint32_t width, uint32_t table_size)
+{
+    return subsample_size(width, table_size <= 2 ? 3 : (table_size <= 4 ? 2 : (table_size <= 16 ? 1 : 0)));
+}
+
+bool inverse_sizes_ok(const Coded& c)
+{
+    if (c.width == 0 || c.height == 0 || c.width > 16384 || c.height > 16384 || c.tf.size() > 4) return false;
+    uint32_t seen = 0, w = c.width;
+    for (const CodedTransform& t : c.tf) {  // bitstream order: the working width shrinks at the indexing transform
+        if (t.type > 3 || (seen >> t.type & 1u)) return false;
+        seen |= 1u << t.type;
+        if (t.type == T_PREDICTOR || t.type == T_COLOR) {
+            if (t.bits < 2 || t.bits > 9) return false;
+            if (t.data.size() < (size_t)subsample_size(w, t.bits) * subsample_size(c.height, t.bits) * 4) return false;
+        } else if (t.type == T_COLOR_INDEXING) {
+            if (t.bits < 1 || t.bits > 256 || t.data.size() < (size_t)t.bits * 4) return false;
+            w = packed_width(w, t.bits);
+        }
+    }
+    return w == c.tw;
+}
+
+void inverse_transforms(uint8_t* px, const Coded& c)
+{
+    uint32_t w = c.tw;
+    for (size_t k = c.tf.size(); k-- > 0;) {
+        const CodedTransform& T = c.tf[k];
+        switch (T.type) {
+        case T_PREDICTOR: inverse_predictor(px, w, c.height, T.bits, T.data.data()); break;
+        case T_COLOR: inverse_color(px, w, c.height, T.bits, T.data.data()); break;
         case T_SUBTRACT_GREEN:  // apply_subtract_green_transform (lossless_transform.rs:395-400)
-            for (size_t i = 0; i < (size_t)w * D.height; i++) {
-                rgba[i * 4] = (uint8_t)(rgba[i * 4] + rgba[i * 4 + 1]);
-                rgba[i * 4 + 2] = (uint8_t)(rgba[i * 4 + 2] + rgba[i * 4 + 1]);
+            for (size_t i = 0; i < (size_t)w * c.height; i++) {
+                px[i * 4] = (uint8_t)(px[i * 4] + px[i * 4 + 1]);
+                px[i * 4 + 2] = (uint8_t)(px[i * 4 + 2] + px[i * 4 + 1]);
             }
             break;
         default:
-            w = D.width;
-            inverse_color_indexing(rgba.data(), w, D.height, T.table_size, T.data.data());
+            w = c.width;
+            inverse_color_indexing(px, w, c.height, T.bits, T.data.data());
             break;
         }
     }
+}
+
+namespace {
+
+// decode_frame: the split read, then the host inverses
+int decode_frame_impl(const uint8_t* data, size_t len, uint32_t width, uint32_t height, bool implicit_dims,
+                      std::vector<uint8_t>& rgba, std::vector<uint8_t>* transforms)
+{
+    Coded c;
+    const int r = decode_coded_impl(data, len, width, height, implicit_dims, nullptr, 0, &rgba, c);
+    if (transforms) {
+        transforms->clear();
+        for (const CodedTransform& t : c.tf) transforms->push_back((uint8_t)t.type);
+    }
+    if (r) return r;
+    inverse_transforms(rgba.data(), c);
     return ZW_OK;
 }
 
 }  // namespace
 
-int read_header(const uint8_t* data, size_t len, uint32_t* width, uint32_t* height)
+int decode_coded(const uint8_t* data, size_t len, uint32_t width, uint32_t height, bool implicit_dims, uint8_t* px,
+                 size_t cap, Coded& out)
 {
-    BitReader br(data, len);
-    return header(br, width, height);
+    if (!px || (!data && len)) return ZW_EINVAL;
+    try {
+        return decode_coded_impl(data, len, width, height, implicit_dims, px, cap, nullptr, out);
+    } catch (const std::bad_alloc&) {
+        return ZW_ENOMEM;
+    }
 }
 
 int decode_frame(const uint8_t* data, size_t len, uint32_t width, uint32_t height, bool implicit_dims,
@@ -696,5 +773,81 @@ extern "C" int zw_dbg_vp8l_decode(const uint8_t* data, size_t len, uint32_t* arg
     for (size_t i = 0; i < n; i++)
         argb_out[i] = ((uint32_t)rgba[i * 4 + 3] << 24) | ((uint32_t)rgba[i * 4] << 16) |
                       ((uint32_t)rgba[i * 4 + 1] << 8) | rgba[i * 4 + 2];
+    return ZW_OK;
+}
+
+// A hook image as the split reader's Coded (the data copied); false: out of range.
+bool zw_vp8l_hook_image(const zw_vp8l_image& im, uint32_t width, uint32_t height, zwvp8l::Coded& c)
+{
+    if (!im.coded || im.ntransforms < 0 || im.ntransforms > 4) return false;
+    c.width = c.tw = width;
+    c.height = height;
+    c.tf.clear();
+    for (int k = 0; k < im.ntransforms; k++) {
+        const zw_vp8l_transform& t = im.t[k];
+        if (!t.data && t.len) return false;
+        zwvp8l::CodedTransform ct;
+        ct.type = t.type;
+        ct.bits = t.bits;
+        ct.data.assign(t.data, t.data + t.len);
+        if (t.type == 3 && t.bits >= 1 && t.bits <= 256) c.tw = zwvp8l::packed_width(c.tw, t.bits);
+        c.tf.push_back(std::move(ct));
+    }
+    return zwvp8l::inverse_sizes_ok(c);
+}
+
+extern "C" int zw_dbg_vp8l_inverse_host(int n, const zw_vp8l_image* images, uint32_t width, uint32_t height,
+                                        uint8_t* out)
+{
+    if (n <= 0 || !images || !out || width == 0 || height == 0 || width > 16384 || height > 16384) return ZW_EINVAL;
+    const size_t fbytes = (size_t)width * height * 4;
+    try {
+        for (int i = 0; i < n; i++) {
+            zwvp8l::Coded c;
+            if (!zw_vp8l_hook_image(images[i], width, height, c)) return ZW_EINVAL;
+            uint8_t* px = out + (size_t)i * fbytes;
+            memmove(px, images[i].coded, (size_t)c.tw * height * 4);
+            zwvp8l::inverse_transforms(px, c);
+        }
+    } catch (const std::bad_alloc&) {
+        return ZW_ENOMEM;
+    }
+    return ZW_OK;
+}
+
+extern "C" int zw_dbg_vp8l_read_coded(const uint8_t* data, size_t len, zw_bytes* out)
+{
+    if (!out || (!data && len)) return ZW_EINVAL;
+    out->data = nullptr;
+    out->len = 0;
+    uint32_t w = 0, h = 0;
+    if (int r = zwvp8l::read_header(data, len, &w, &h)) return r;
+    try {
+        std::vector<uint8_t> px((size_t)w * h * 4);
+        zwvp8l::Coded c;
+        if (int r = zwvp8l::decode_coded(data, len, 0, 0, false, px.data(), px.size(), c)) return r;
+        std::vector<uint8_t> blob;
+        auto word = [&](uint32_t v) {
+            for (int k = 0; k < 4; k++) blob.push_back((uint8_t)(v >> (8 * k)));
+        };
+        const uint32_t head[8] = {c.width, c.height, c.tw, (uint32_t)c.tf.size(), 0, 0, 0, 0};
+        for (uint32_t v : head) word(v);
+        for (const zwvp8l::CodedTransform& t : c.tf) {
+            word(t.type);
+            word(t.bits);
+            word((uint32_t)t.data.size());
+            word(0);
+            blob.insert(blob.end(), t.data.begin(), t.data.end());
+            while (blob.size() & 3) blob.push_back(0);
+        }
+        blob.insert(blob.end(), px.begin(), px.begin() + (size_t)c.tw * c.height * 4);
+        uint8_t* p = (uint8_t*)malloc(blob.size());
+        if (!p) return ZW_ENOMEM;
+        memcpy(p, blob.data(), blob.size());
+        out->data = p;
+        out->len = blob.size();
+    } catch (const std::bad_alloc&) {
+        return ZW_ENOMEM;
+    }
     return ZW_OK;
 }

@@ -123,6 +123,20 @@ class _WebpInfoEx(ctypes.Structure):
 
 
 WEBP_ALPHA = 1  # ZW_WEBP_ALPHA
+WEBP_LOSSLESS = 4  # ZW_WEBP_LOSSLESS
+
+
+def _webp_flags(alpha, lossless):
+    return (WEBP_ALPHA if alpha else 0) | (WEBP_LOSSLESS if lossless else 0)
+
+
+class _Vp8lTransform(ctypes.Structure):
+    _fields_ = [("type", ctypes.c_uint32), ("bits", ctypes.c_uint32), ("data", ctypes.c_void_p),
+                ("len", ctypes.c_size_t)]
+
+
+class _Vp8lImage(ctypes.Structure):
+    _fields_ = [("coded", ctypes.c_void_p), ("ntransforms", ctypes.c_int), ("t", _Vp8lTransform * 4)]
 
 
 class _DeviceImages(ctypes.Structure):
@@ -233,6 +247,10 @@ SIGNATURES = [
     ("zw_dbg_alph_plane", _I, [_VP, _SZ, _U32, _U32, _VP, ctypes.POINTER(_I)]),
     ("zw_dbg_vp8l_decode", _I, [_VP, _SZ, _VP, ctypes.POINTER(_U32), ctypes.POINTER(_U32)]),
     ("zw_decode_alpha_times", _I, [_VP, ctypes.POINTER(ctypes.c_float)]),
+    ("zw_decode_lossless_times", _I, [_VP, ctypes.POINTER(ctypes.c_float)]),
+    ("zw_dbg_vp8l_inverse_host", _I, [_I, ctypes.POINTER(_Vp8lImage), _U32, _U32, _VP]),
+    ("zw_dbg_vp8l_inverse_device", _I, [_VP, _I, ctypes.POINTER(_Vp8lImage), _U32, _U32, _VP]),
+    ("zw_dbg_vp8l_read_coded", _I, [_VP, _SZ, ctypes.POINTER(_Bytes)]),
 ]
 
 _LIB = None
@@ -730,7 +748,7 @@ def decode_batch_device_ptr(frames, ptr, capacity, width=None, height=None, chan
 
 
 def decode_batch_device(frames, out=None, channels=3, layout="chw", dtype="u8", upsampling=UpsamplingMethod.Bilinear,
-                        scale=None, bias=None, ctx=None, _webp=None):
+                        scale=None, bias=None, ctx=None, _webp=None, _dims=None):
     """n VP8 key frames of one size decoded straight into a torch tensor on the
     context's device, with no download, upload or host copy
     (zw_vp8_decode_batch_device; the values are decode_batch_device_ptr's).
@@ -759,6 +777,8 @@ def decode_batch_device(frames, out=None, channels=3, layout="chw", dtype="u8", 
     a0 = arrs[0]
     w = int(a0[6]) | ((int(a0[7]) & 0x3F) << 8) if a0.size >= 10 else 0
     h = int(a0[8]) | ((int(a0[9]) & 0x3F) << 8) if a0.size >= 10 else 0
+    if _dims is not None:  # (whole files that may be lossless: the size the container parse gave)
+        w, h = int(_dims[0]), int(_dims[1])
     webp_flags = None
     if _webp is not None:  # (frames = the files' VP8 payloads, for the size; the call takes the files)
         arrs, webp_flags = _webp
@@ -799,7 +819,8 @@ def decode_batch_device(frames, out=None, channels=3, layout="chw", dtype="u8", 
 
 
 def decode_webp_batch_device(files, out=None, channels=3, layout="chw", dtype="u8",
-                             upsampling=UpsamplingMethod.Bilinear, scale=None, bias=None, ctx=None, alpha=False):
+                             upsampling=UpsamplingMethod.Bilinear, scale=None, bias=None, ctx=None, alpha=False,
+                             lossless=False):
     """decode_batch_device over lossy WebP files: each RIFF container is
     stripped with webp_parse (vp8_offset / vp8_len).  ALPH, VP8L and animated
     files raise DecodingError code 5, as webp_parse does.
@@ -808,18 +829,26 @@ def decode_webp_batch_device(files, out=None, channels=3, layout="chw", dtype="u
     ALPH chunk decode too; `channels` (or the tensor's) must be 4, and channel 3
     holds each file's alpha (255 for a file without the alpha flag) by the same
     store rule as the colours (u8 the byte; f32 a * scale[3] + bias[3]; f16 that
-    rounded to nearest even).  VP8L and animated files still raise code 5; a
-    file with the alpha flag but no ALPH chunk raises code 20."""
-    vp8, arrs = [], []
+    rounded to nearest even).  VP8L files (without lossless=True) and animated files raise code 5; a
+    file with the alpha flag but no ALPH chunk raises code 20.
+
+    lossless=True (ZW_WEBP_LOSSLESS): lossless (VP8L) files decode too, alone or
+    mixed with lossy files of the same size, into 3 or 4 channels: the entropy
+    decode on the host threads, the inverse transforms and the store on the
+    device.  Channel 3 holds the decoded alpha of a file whose has_alpha is set
+    and 255 otherwise.  Animated files still raise code 5."""
+    vp8, arrs, dims = [], [], None
     for f in files:
         a = _as_u8(f)
-        info = webp_parse(a, alpha=alpha)
+        info = webp_parse(a, alpha=alpha, lossless=lossless)
         arrs.append(a)
         vp8.append(a[info["vp8_offset"]:info["vp8_offset"] + info["vp8_len"]])
-    if not alpha:
+        if dims is None:
+            dims = (info["width"], info["height"])
+    if not alpha and not lossless:
         return decode_batch_device(vp8, out, channels, layout, dtype, upsampling, scale, bias, ctx)
     return decode_batch_device(vp8, out, channels, layout, dtype, upsampling, scale, bias, ctx,
-                               _webp=(arrs, WEBP_ALPHA))
+                               _webp=(arrs, _webp_flags(alpha, lossless)), _dims=dims if lossless else None)
 
 
 def decode_batch_device_resized_ptr(frames, ptr, capacity, out_w, out_h, windows=None, channels=3, layout="chw",
@@ -1121,15 +1150,17 @@ def decode_rgb_kernel_ms(ctx=None):
     return float(ms.value)
 
 
-def webp_parse(data, alpha=False):
+def webp_parse(data, alpha=False, lossless=False):
     """WebPDecoder::new's container parse (decoder/api.rs:334-510): dict of the header facts.
     alpha=True (zw_webp_parse_ex with ZW_WEBP_ALPHA): a lossy file with the alpha
-    flag parses too, and the dict also holds alph_offset / alph_len."""
+    flag parses too, and the dict also holds alph_offset / alph_len.
+    lossless=True (ZW_WEBP_LOSSLESS): a still VP8L image parses too; vp8_offset /
+    vp8_len then give its VP8L payload."""
     L = load_library()
     a = _as_u8(data)
-    if alpha:
+    if alpha or lossless:
         ex = _WebpInfoEx()
-        rc = L.zw_webp_parse_ex(_ptr(a) if a.size else None, a.size, WEBP_ALPHA, ctypes.byref(ex))
+        rc = L.zw_webp_parse_ex(_ptr(a) if a.size else None, a.size, _webp_flags(alpha, lossless), ctypes.byref(ex))
         _check(rc, "WebPDecoder::new", DecodingError)
         return {f: getattr(ex, f) for f, _ in _WebpInfoEx._fields_}
     info = _WebpInfo()
@@ -1138,13 +1169,14 @@ def webp_parse(data, alpha=False):
     return {f: getattr(info, f) for f, _ in _WebpInfo._fields_}
 
 
-def _webp_decode(data, bpp, upsampling, ctx, alpha=False):
+def _webp_decode(data, bpp, upsampling, ctx, alpha=False, lossless=False):
     c = _ctx(ctx)
     L = c._lib
     a = _as_u8(data)
     out, w, h = _Bytes(), ctypes.c_uint32(), ctypes.c_uint32()
-    if alpha:
-        _check(L.zw_webp_decode_ex(c.handle, _ptr(a) if a.size else None, a.size, bpp, upsampling, WEBP_ALPHA,
+    if alpha or lossless:
+        _check(L.zw_webp_decode_ex(c.handle, _ptr(a) if a.size else None, a.size, bpp, upsampling,
+                                   _webp_flags(alpha, lossless),
                                    ctypes.byref(out), ctypes.byref(w), ctypes.byref(h)), "decode", DecodingError)
     else:
         _check(L.zw_webp_decode(c.handle, _ptr(a) if a.size else None, a.size, bpp, upsampling, ctypes.byref(out),
@@ -1152,10 +1184,11 @@ def _webp_decode(data, bpp, upsampling, ctx, alpha=False):
     return _take_image(L, out, w.value, h.value, bpp), w.value, h.value
 
 
-def decode_rgba(data, ctx=None, alpha=False):
+def decode_rgba(data, ctx=None, alpha=False, lossless=False):
     """decode_rgba (decoder/api.rs:938): (flat RGBA bytes, width, height); lossy files.
-    alpha=True: a file with an ALPH chunk decodes with its alpha (zw_webp_decode_ex)."""
-    img, w, h = _webp_decode(data, 4, UpsamplingMethod.Bilinear, ctx, alpha)
+    alpha=True: a file with an ALPH chunk decodes with its alpha (zw_webp_decode_ex).
+    lossless=True: a lossless file decodes too (alpha 255 unless its has_alpha is set)."""
+    img, w, h = _webp_decode(data, 4, UpsamplingMethod.Bilinear, ctx, alpha, lossless)
     return img.reshape(-1), w, h
 
 
@@ -1202,9 +1235,83 @@ def decode_alpha_times(ctx=None):
     return float(ms[0]), float(ms[1]), float(ms[2])
 
 
-def decode_rgb(data, ctx=None):
-    """decode_rgb (decoder/api.rs:973): (flat RGB bytes, width, height); lossy files."""
-    img, w, h = _webp_decode(data, 3, UpsamplingMethod.Bilinear, ctx)
+def decode_lossless_times(ctx=None):
+    """zw_decode_lossless_times: (host entropy decode ms, transform kernels ms, store kernel ms) of the last
+    lossless decode."""
+    c = _ctx(ctx)
+    ms = (ctypes.c_float * 3)()
+    _check(c._lib.zw_decode_lossless_times(c.handle, ms), "decode_lossless_times")
+    return float(ms[0]), float(ms[1]), float(ms[2])
+
+
+def _vp8l_images(images):
+    """[(coded (h, tw, 4) u8, [(type, bits, data u8 array or None), ...]), ...] as the C hooks take them."""
+    n = len(images)
+    arr = (_Vp8lImage * n)()
+    keep = []
+    for i, (coded, tfs) in enumerate(images):
+        c = np.ascontiguousarray(coded, np.uint8)
+        keep.append(c)
+        arr[i].coded = c.ctypes.data
+        arr[i].ntransforms = len(tfs)
+        for k, (typ, bits, data) in enumerate(tfs):
+            d = np.ascontiguousarray(data if data is not None else np.zeros(0, np.uint8), np.uint8)
+            keep.append(d)
+            arr[i].t[k].type = int(typ)
+            arr[i].t[k].bits = int(bits)
+            arr[i].t[k].data = d.ctypes.data if d.size else None
+            arr[i].t[k].len = d.size
+    return arr, keep
+
+
+def dbg_vp8l_inverse_host(images, width, height):
+    """zw_dbg_vp8l_inverse_host (host only): the inverse transforms of n coded images of one canvas size;
+    images = [(coded pixels u8 R, G, B, A of tw * height pixels, [(type, bits, data), ...] in bitstream
+    order), ...].  Returns (n, height, width, 4) u8."""
+    L = load_library()
+    arr, keep = _vp8l_images(images)
+    out = np.empty((len(images), int(height), int(width), 4), np.uint8)
+    _check(L.zw_dbg_vp8l_inverse_host(len(images), arr, int(width), int(height), out.ctypes.data),
+           "dbg_vp8l_inverse_host", DecodingError)
+    return out
+
+
+def dbg_vp8l_inverse_device(images, width, height, ctx=None):
+    """zw_dbg_vp8l_inverse_device: the same through the transform kernels, all images in one chunk."""
+    c = _ctx(ctx)
+    arr, keep = _vp8l_images(images)
+    out = np.empty((len(images), int(height), int(width), 4), np.uint8)
+    _check(c._lib.zw_dbg_vp8l_inverse_device(c.handle, len(images), arr, int(width), int(height), out.ctypes.data),
+           "dbg_vp8l_inverse_device", DecodingError)
+    return out
+
+
+def dbg_vp8l_read_coded(data):
+    """zw_dbg_vp8l_read_coded (host only): a headered VP8L stream read up to its transforms:
+    (width, height, coded (height, tw, 4) u8, [(type, bits, data u8), ...] in bitstream order)."""
+    L = load_library()
+    a = _as_u8(data)
+    b = _Bytes()
+    _check(L.zw_dbg_vp8l_read_coded(_ptr(a) if a.size else None, a.size, ctypes.byref(b)), "dbg_vp8l_read_coded",
+           DecodingError)
+    blob = _take_bytes(L, b)
+    blob = np.frombuffer(blob, np.uint8)
+    head = blob[:32].view("<u4")
+    w, h, tw, ntf = (int(v) for v in head[:4])
+    pos, tfs = 32, []
+    for _ in range(ntf):
+        typ, bits, nb, _pad = (int(v) for v in blob[pos:pos + 16].view("<u4"))
+        pos += 16
+        tfs.append((typ, bits, blob[pos:pos + nb].copy()))
+        pos += (nb + 3) & ~3
+    coded = blob[pos:pos + tw * h * 4].reshape(h, tw, 4).copy()
+    return w, h, coded, tfs
+
+
+def decode_rgb(data, ctx=None, lossless=False):
+    """decode_rgb (decoder/api.rs:973): (flat RGB bytes, width, height); lossy files,
+    and with lossless=True lossless ones (their alpha dropped)."""
+    img, w, h = _webp_decode(data, 3, UpsamplingMethod.Bilinear, ctx, False, lossless)
     return img.reshape(-1), w, h
 
 
@@ -1212,11 +1319,12 @@ class WebPDecoder:
     """WebPDecoder (decoder/api.rs:306-906), lossy subset: new / dimensions / has_alpha /
     is_lossy / output_buffer_size / set_lossy_upsampling / read_image."""
 
-    def __init__(self, data, ctx=None, alpha=False):
+    def __init__(self, data, ctx=None, alpha=False, lossless=False):
         self._data = _as_u8(data)
         self._ctx = ctx
         self._alpha = bool(alpha)  # lossy files with an ALPH chunk open and decode to RGBA (api.rs:672-700)
-        self._info = webp_parse(self._data, alpha=self._alpha)
+        self._lossless = bool(lossless)  # lossless files open and decode to RGB or RGBA (api.rs:648-660)
+        self._info = webp_parse(self._data, alpha=self._alpha, lossless=self._lossless)
         self._up = UpsamplingMethod.Bilinear
 
     def dimensions(self):
@@ -1238,7 +1346,7 @@ class WebPDecoder:
     def read_image(self, buf=None):
         """Decodes into `buf` (a writable u8 buffer of output_buffer_size()) or returns a new array."""
         bpp = 4 if self.has_alpha() else 3
-        img, _, _ = _webp_decode(self._data, bpp, self._up, self._ctx, self._alpha and bpp == 4)
+        img, _, _ = _webp_decode(self._data, bpp, self._up, self._ctx, self._alpha and bpp == 4, self._lossless)
         flat = img.reshape(-1)
         if buf is None:
             return flat

@@ -20,6 +20,9 @@
  *   zw_webp_parse_ex / zw_webp_decode_ex / zw_webp_decode_batch_device (flag ZW_WEBP_ALPHA)
  *                           read_image of a lossy file with alpha  src/decoder/api.rs:661-703,
  *                           read_alpha_chunk / get_alpha_predictor  src/decoder/extended.rs:151-334
+ *   ... the same three entries (flag ZW_WEBP_LOSSLESS)
+ *                           read_image of a lossless file  src/decoder/api.rs:648-660,
+ *                           LosslessDecoder::decode_frame  src/decoder/lossless.rs:92-177
  *   zw_yuv_to_rgb           fill_rgb_buffer_fancy/_simple  src/decoder/yuv.rs:82 / :402
  *   zw_rgb_to_yuv420        convert_image_yuv/_y      src/decoder/yuv.rs:656 / :806
  *   zw_loop_filter_frame    filter_row_in_cache       src/decoder/vp8.rs:1172-1345
@@ -419,7 +422,8 @@ int zw_webp_decode_into(zw_ctx *ctx, const uint8_t *data, size_t len, int bpp, i
  * green channel is the plane: read_alpha_chunk, decoder/extended.rs:273-334)
  * runs on the host threads; the alpha filter is undone (get_alpha_predictor,
  * extended.rs:151-211: out = predictor + residual mod 256) and channel 3 is
- * written on the device.  Still VP8L images and animation stay ZW_EUNSUPPORTED. */
+ * written on the device.  VP8L images need ZW_WEBP_LOSSLESS (below); animation
+ * stays ZW_EUNSUPPORTED. */
 enum { ZW_WEBP_ALPHA = 1 };
 typedef struct {
     uint32_t width, height; /* canvas */
@@ -431,7 +435,7 @@ typedef struct {
  * filled as far as the scan went).  ZW_WEBP_ALPHA: a VP8X file with the alpha
  * flag and a "VP8 " chunk parses; the flag without an ALPH chunk is
  * ZW_ECHUNK_MISSING (the reference, api.rs:675-678; libwebp would decode it as
- * opaque).  Any other flag bit: ZW_EINVAL. */
+ * opaque).  ZW_WEBP_LOSSLESS: see below.  Any other flag bit: ZW_EINVAL. */
 int zw_webp_parse_ex(const uint8_t *data, size_t len, int flags, zw_webp_info_ex *info);
 /* n whole WebP files of one size into the caller's device memory: the output,
  * its addressing and every check are zw_vp8_decode_batch_device's, on the files'
@@ -470,6 +474,76 @@ int zw_dbg_vp8l_decode(const uint8_t *data, size_t len, uint32_t *argb_out, uint
  * (device time, summed over the chunks).  zw_decode_rgb_kernel_ms of such a
  * call spans the colour conversion and the chunk's alpha upload and kernels. */
 int zw_decode_alpha_times(zw_ctx *ctx, float *ms);
+/* ---- Lossless files (VP8L images), opt-in ----
+ * ZW_WEBP_LOSSLESS = 4 in `flags` of zw_webp_parse_ex, zw_webp_decode_batch_device
+ * and zw_webp_decode_ex (value 2 is not a flag: it stays ZW_EINVAL, as every
+ * other unknown bit).  WebPDecoder::read_image of a lossless file
+ * (decoder/api.rs:648-660) through LosslessDecoder::decode_frame.
+ *
+ * zw_webp_parse_ex with the flag: a simple "VP8L" file and a VP8X file whose
+ * image is a "VP8L" chunk parse; is_lossless = 1, is_lossy = 0, vp8_offset /
+ * vp8_len give the VP8L payload, width / height the header's (simple) or the
+ * canvas (VP8X); has_alpha is bit 28 of the VP8L header for a simple file
+ * (api.rs:395) and the VP8X flag for an extended one.  A wrong signature byte
+ * is ZW_ELOSSLESS_SIGNATURE, a version other than 0 ZW_EVERSION_NUMBER
+ * (api.rs:378-395).  Without the flag every code and field is as before.
+ *
+ * zw_webp_decode_batch_device with the flag: lossless files decode into the
+ * caller's tensor (3 or 4 channels; ZW_WEBP_ALPHA still needs 4).  The entropy
+ * decode (Huffman groups, colour cache, LZ77: a serial bit chain) runs on the
+ * host threads, one file per task, into pinned staging; the inverse transforms
+ * (predictor, cross-colour, subtract-green, colour indexing, in reverse
+ * bitstream order) and the store run on the device (csrc/zw_vp8l_kernels.hip),
+ * chunk k's device work beside chunk k + 1's host decode.  The store follows
+ * the rule above: u8 the byte; f32 float32(v) * scale[c] + bias[c], a rounded
+ * multiply then a rounded add; f16 that float rounded to nearest even; HWC or
+ * CHW with the caller's strides, the gaps never written.  Channel 3 holds the
+ * decoded alpha byte when has_alpha is set and 255 when it is not (the
+ * reference drops the decoded A then, api.rs:652-660); 3 channels drop it.
+ * A batch may mix lossy and lossless files of one size: the call splits it
+ * into maximal runs of one kind, one pass per run, each run writing at its own
+ * frame offset.  A canvas that disagrees with the VP8L header's size is
+ * ZW_EINCONSISTENT_SIZES; a damaged stream returns its decoder code.
+ *
+ * zw_webp_decode_ex with the flag: a lossless file to a packed host image, bpp
+ * 3 or 4, through the same device path and one download.
+ *
+ * Still ZW_EUNSUPPORTED: animation, and lossless input to the _resized entries. */
+enum { ZW_WEBP_LOSSLESS = 4 };
+/* Host entropy decode (wall ms over the chunks), transform kernels and store
+ * kernels (device ms) of the last lossless decode on ctx. */
+int zw_decode_lossless_times(zw_ctx *ctx, float *ms);
+/* Test hooks for the inverse transforms; they take no bitstream.  An image is
+ * its coded pixels (tw * height pixels R, G, B, A; tw = the canvas width, packed
+ * by every colour indexing transform's table: 8 / 4 / 2 / 1 indices per pixel
+ * for tables of <= 2 / 4 / 16 / 256 entries) and its transforms in bitstream
+ * order.  type: 0 predictor, 1 cross-colour, 2 subtract-green, 3 colour
+ * indexing; bits: size_bits (2..9) of types 0 and 1, table_size (1..256) of
+ * type 3; data: the sub-image (ceil(w / 2^bits) x ceil(height / 2^bits) pixels
+ * R, G, B, A, w the working width at that transform) or the table.  out: n *
+ * width * height pixels R, G, B, A.  ZW_EINVAL for sizes out of range, a type
+ * given twice or data shorter than its sub-image.
+ * zw_dbg_vp8l_inverse_host runs the host inverses (no device work);
+ * zw_dbg_vp8l_inverse_device uploads all n images as one chunk, runs the
+ * transform kernels over the per-transform frame lists and downloads.
+ * zw_dbg_vp8l_read_coded (host only) reads a headered VP8L stream up to the
+ * transforms: out = 8 little-endian u32 words (width, height, tw, ntransforms,
+ * 0, 0, 0, 0), then per transform 4 words (type, bits, data bytes, 0) and its
+ * data padded to 4 bytes, then the coded image. */
+typedef struct {
+    uint32_t type, bits;
+    const uint8_t *data;
+    size_t len;
+} zw_vp8l_transform;
+typedef struct {
+    const uint8_t *coded;
+    int ntransforms; /* 0..4 */
+    zw_vp8l_transform t[4];
+} zw_vp8l_image;
+int zw_dbg_vp8l_inverse_host(int n, const zw_vp8l_image *images, uint32_t width, uint32_t height, uint8_t *out);
+int zw_dbg_vp8l_inverse_device(zw_ctx *ctx, int n, const zw_vp8l_image *images, uint32_t width, uint32_t height,
+                               uint8_t *out);
+int zw_dbg_vp8l_read_coded(const uint8_t *data, size_t len, zw_bytes *out);
 /* Device time (HIP events on the context stream) of the last decode batch:
  * ms[0] = k_dec_recon (dequant + iWHT/iDCT + prediction), ms[1] = k_loopfilter. */
 int zw_decode_kernel_times(zw_ctx *ctx, float *ms);
