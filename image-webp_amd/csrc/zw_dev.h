@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "zw_common.h"
+#include "zw_enc_i4pair.h"
 
 #define ZW_TABLE(T, N, D, ...) __constant__ T d_##N D = {__VA_ARGS__};
 #include "zw_tables.inc"
@@ -15,18 +16,8 @@
 // 255 = DC, 254 = TM.  Value vector: E = [L3 L2 L1 L0 P A0..A7], then
 // avg3 of consecutive triples (13..23), avg2 of pairs (24..35),
 // avg3(A6,A7,A7) (36), avg3(L2,L3,L3) (37).
-__constant__ uint8_t d_I4_IDX[10][16] = {
-    {255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255, 255},
-    {254, 254, 254, 254, 254, 254, 254, 254, 254, 254, 254, 254, 254, 254, 254, 254},
-    {17, 18, 19, 20, 17, 18, 19, 20, 17, 18, 19, 20, 17, 18, 19, 20},
-    {15, 15, 15, 15, 14, 14, 14, 14, 13, 13, 13, 13, 37, 37, 37, 37},
-    {18, 19, 20, 21, 19, 20, 21, 22, 20, 21, 22, 23, 21, 22, 23, 36},
-    {16, 17, 18, 19, 15, 16, 17, 18, 14, 15, 16, 17, 13, 14, 15, 16},
-    {28, 29, 30, 31, 16, 17, 18, 19, 15, 28, 29, 30, 14, 16, 17, 18},
-    {29, 30, 31, 32, 18, 19, 20, 21, 30, 31, 32, 22, 19, 20, 21, 23},
-    {27, 16, 17, 18, 26, 15, 27, 16, 25, 14, 26, 15, 24, 13, 25, 14},
-    {26, 14, 25, 13, 25, 13, 24, 37, 24, 37, 0, 0, 0, 0, 0, 0},
-};
+// The rows are in zw_enc_i4pair.h, where the host tools read them too.
+__constant__ uint8_t d_I4_IDX[10][16] = {ZW_I4_IDX_ROWS};
 
 #define DI __device__ __forceinline__
 
@@ -357,8 +348,8 @@ struct LdsTables {
     uint16_t lfc[2048];       // VP8_LEVEL_FIXED_COSTS
     uint16_t ent[256];        // VP8_ENTROPY_COST
     uint16_t fci4[10][10][10];  // VP8_FIXED_COSTS_I4
-    uint8_t i4idx[10][16];    // d_I4_IDX
     uint8_t i4qa[10][16];     // 4 x the V index of pixel p under mode m (254 -> 3 - row, 255 -> 38)
+    uint8_t i4qp[10][16];     // the same for the paired search's value vector (i4p_vindex, zw_enc_i4pair.h)
     uint8_t zz[16];           // ZIGZAG
     uint8_t bands[17];        // VP8_ENC_BANDS
     uint8_t izz[16];          // inverse zigzag: natural index -> position
@@ -380,8 +371,8 @@ DI void load_static_tables(LdsTables* T, int tid, int nt, const uint8_t* probs /
     for (int i = tid; i < 1000; i += nt) (&T->fci4[0][0][0])[i] = (&d_VP8_FIXED_COSTS_I4[0][0][0])[i];
     for (int i = tid; i < 160; i += nt) {
         const int idx = (&d_I4_IDX[0][0])[i], p = i & 15;
-        (&T->i4idx[0][0])[i] = (uint8_t)idx;
         (&T->i4qa[0][0])[i] = (uint8_t)(4 * (idx == 254 ? 3 - (p >> 2) : (idx == 255 ? 38 : idx)));
+        (&T->i4qp[0][0])[i] = (uint8_t)(4 * i4p_vindex(idx, p));
     }
     for (int i = tid; i < 16; i += nt) T->zz[i] = d_ZIGZAG[i];
     for (int i = tid; i < 17; i += nt) T->bands[i] = d_VP8_ENC_BANDS[i];

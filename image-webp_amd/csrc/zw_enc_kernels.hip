@@ -405,9 +405,8 @@ __device__ __forceinline__ int bperm(int v, int src_lane) { return __builtin_amd
 // (pred = clamp(V[ia] + V[5 + col] - V[4])).  Sub-block independent.
 __device__ __forceinline__ int i4_src_index(const LdsTables* T, int mode, int p)
 {
-    const int idx = T->i4idx[mode][p];
-    const bool tm = idx == 254;
-    return csel(tm, 256 + 3 - (p >> 2), csel(idx == 255, 38, idx));
+    // (TrueMotion is mode 1, the only row of d_I4_IDX that holds 254; i4qa is 4 x the index)
+    return (T->i4qa[mode][p] >> 2) + csel(mode == 1, 256, 0);
 }
 __device__ __forceinline__ int i4_pred_at(const int* V, int sidx, int vbc)
 {
@@ -1220,7 +1219,10 @@ __device__ bool pick_i4(const Ctx& C, unsigned long long i16_score, bool keep, u
 // keeps the quad form (lane = 32 hm + 16 slot + 4 k + q), the ranking works
 // all four rows of a (slot, mode) in one lane (lane = 32 hm + 16 slot + mode).
 // The value vectors of the four (MB, slot) blocks are packed one byte each
-// (byte 2 hm + slot) in lanes 0..38.  Every per-MB decision (winners, early
+// (byte 2 hm + slot) in lanes 0..54: every prediction of every mode is a plain
+// read of an entry, TrueMotion's sixteen clamped sums included (lanes 39..54),
+// and the ranking orders the modes by byte dot products of the packed rows
+// (zw_enc_i4pair.h).  Every per-MB decision (winners, early
 // exits, running scores) is the single search's, per MB: a search that ends
 // early leaves its lanes computing on, with their stores masked.
 // A step stays in the lanes from its values to the next step's contexts
@@ -1232,19 +1234,18 @@ __device__ bool pick_i4(const Ctx& C, unsigned long long i16_score, bool keep, u
 struct I4PLane {
     uint32_t ix[4];  // bperm byte addresses (4 x V index) of the lane's pixels in rows 0..3, one per byte
     uint32_t psel;   // v_perm selector taking the lane's (MB, slot) byte of two gathered words
+#if ZW_I4P_DOT4 && ZW_I4P_TMV
+    uint32_t bsel;   // ... to bytes 0 and 1 (the ranking's packed rows)
+#endif
+#if !ZW_I4P_TMV
     int tm;          // mode is TrueMotion
+#endif
     // the candidate step's quantiser of the lane's coefficient column q (its MB's
     // segment, fixed for the search): read once instead of every step
     uint32_t iq0, bs0, iq1, bs1;
     int q0, qa;
     uint32_t l_i4;
 };
-
-DI uint32_t i4p_psel(int hm, int slot)
-{
-    const uint32_t b = (uint32_t)(2 * hm + slot);
-    return 0x0c000c00u | ((4u + b) << 16) | b;
-}
 
 DI void i4p_lane_init(const Ctx& C, const Ctx& CB, I4PLane& L)
 {
@@ -1260,36 +1261,29 @@ DI void i4p_lane_init(const Ctx& C, const Ctx& CB, I4PLane& L)
         L.qa = (int)Sh->y1.q[1];
         L.l_i4 = Sh->l_i4;
     }
+    // (the static tables of both frames are alike)
 #pragma unroll
-    for (int r = 0; r < 4; r++) {
-        uint32_t w = 0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) w |= (uint32_t)(4 * (i4_src_index(C.T, mv, 4 * r + j) & 255)) << (8 * j);
-        L.ix[r] = w;
-    }
+    for (int r = 0; r < 4; r++) L.ix[r] = *(const uint32_t*)&C.T->i4qp[mv][4 * r];
     L.psel = i4p_psel(l >> 5, (l >> 4) & 1);
+#if ZW_I4P_DOT4 && ZW_I4P_TMV
+    L.bsel = i4p_bsel(l >> 5, (l >> 4) & 1);
+#endif
+#if !ZW_I4P_TMV
     L.tm = mv == 1;
+#endif
 }
 
-// Value vectors (see i4_values_pk) of both MBs' step blocks: lane v < 39 holds
-// V[v] of (A slot 0, A slot 1, B slot 0, B slot 1) in bytes 0..3.
+// Value vectors (zw_enc_i4pair.h) of both MBs' step blocks: lane v < ZW_I4P_NV
+// holds V[v] of (A slot 0, A slot 1, B slot 0, B slot 1) in bytes 0..3.
 template <int NB>
 DI uint32_t i4p_values(const Ctx& CA, const Ctx& CB, const int* x0, const int* y0)
 {
     const int l = CA.lane;
-    const int t = (int)(l >= 13) + (int)(l >= 24) + (int)(l >= 36) + (int)(l >= 37);
-    const int k = min(l - 13 * (int)(l >= 13) - 11 * (int)(l >= 24), 12);
-    const int t3 = (int)(t == 3), t4 = (int)(t >= 4), t12 = (int)(t == 1 || t == 2);
-    const int ka = k + t3 * (11 - k) + t4 * (1 - k);
-    const int kb = k + t12 + t3 * (12 - k) - t4 * k;
-    const int kc = min(k + 2 * (int)(t == 1), 12);
-    const int wb = 2 * (int)(t == 1) + (int)(t == 2) + 3 * (t3 + t4);
-    const int wc = (int)(t == 1);
-    const int sh = (int)(t != 0) + (int)(t != 0 && t != 2);
-    const int oa = csel(ka < 4, -ka * ZW_BPS, ka - 4 - 4 * ZW_BPS);
-    const int ob = csel(kb < 4, -kb * ZW_BPS, kb - 4 - 4 * ZW_BPS);
-    const int oc = csel(kc < 4, -kc * ZW_BPS, kc - 4 - 4 * ZW_BPS);
-    const bool dcl = l < 4 || (l >= 5 && l < 9);
+    const I4PValue vm = i4p_value_map(l);
+    const int oa = csel(vm.ka < 4, -vm.ka * ZW_BPS, vm.ka - 4 - 4 * ZW_BPS);
+    const int ob = csel(vm.kb < 4, -vm.kb * ZW_BPS, vm.kb - 4 - 4 * ZW_BPS);
+    const int oc = csel(vm.kc < 4, -vm.kc * ZW_BPS, vm.kc - 4 - 4 * ZW_BPS);
+    const bool dcl = i4p_value_dc_term(l);
     uint32_t v[2], ea[2];
 #pragma unroll
     for (int mb = 0; mb < 2; mb++) {
@@ -1300,7 +1294,7 @@ DI uint32_t i4p_values(const Ctx& CA, const Ctx& CB, const int* x0, const int* y
             const int hh = NB == 2 ? h : 0;
             const int rowL = (y0[hh] + 3) * ZW_BPS + x0[hh] - 1;
             const int a = ws[rowL + oa], eb = ws[rowL + ob], ec = ws[rowL + oc];
-            v[mb] |= (uint32_t)((a + wb * eb + wc * ec + ((1 << sh) >> 1)) >> sh) << (16 * h);
+            v[mb] |= (uint32_t)i4p_value(vm, a, eb, ec) << (16 * h);
             ea[mb] |= (uint32_t)a << (16 * h);
         }
     }
@@ -1309,7 +1303,7 @@ DI uint32_t i4p_values(const Ctx& CA, const Ctx& CB, const int* x0, const int* y
     const uint32_t db = (uint32_t)__builtin_amdgcn_readfirstlane(red16((int)(dcl ? ea[1] : 0u)));
     const uint32_t dcv = (((da & 0xffffu) + 4) >> 3) | ((((da >> 16) + 4) >> 3) << 8) |
                          ((((db & 0xffffu) + 4) >> 3) << 16) | ((((db >> 16) + 4) >> 3) << 24);
-    return l == 38 ? dcv : __builtin_amdgcn_perm(v[1], v[0], 0x06040200u);
+    return l == ZW_I4P_V_DC ? dcv : __builtin_amdgcn_perm(v[1], v[0], 0x06040200u);
 }
 
 // The running state of a paired search: in lane form every lane holds its MB's
@@ -1376,6 +1370,7 @@ DI void i4p_step(const Ctx& CA, const Ctx& CB, const int* sbx, const int* sby, i
     };
     PH_START();
     const uint32_t vp = i4p_values<NB>(CA, CB, x0, y0);
+#if !ZW_I4P_TMV
     // TrueMotion offsets V[5 + j] - V[4] of the lane's (MB, slot), as (x0, x1), (x3, x2) pairs
     uint32_t ap01, ap32;
     {
@@ -1390,12 +1385,17 @@ DI void i4p_step(const Ctx& CA, const Ctx& CB, const int* sbx, const int* sby, i
         ap01 = pack_lo(d0, d1);
         ap32 = pack_lo(d3, d2);
     }
+#endif
     PH_MARK_L(10, l, 0);
 #if ZW_I4P_INV
     read_ctx();  // (before the ranking: its round trips hide these)
 #endif
     // ranking: the four rows of (MB, slot, mode) in one lane
+#if ZW_I4P_DOT4
+    uint32_t pp = 0, sp = 0;  // sum p^2, sum s p: their key orders the modes as the SSE's does (i4p_rank_key)
+#else
     int pse = 0;
+#endif
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         const uint32_t ix = LC.ix[r];
@@ -1403,16 +1403,38 @@ DI void i4p_step(const Ctx& CA, const Ctx& CB, const int* sbx, const int* sby, i
         const uint32_t v1 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((ix >> 8) & 255u), (int)vp);
         const uint32_t v2 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((ix >> 16) & 255u), (int)vp);
         const uint32_t v3 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(ix >> 24), (int)vp);
+        const uint32_t sw = *(const uint32_t*)(sYh + (by * 4 + r) * 16 + bx * 4);
+#if ZW_I4P_DOT4 && ZW_I4P_TMV
+        // the row's four predictions as bytes, in the source row's order
+        const uint32_t b01 = __builtin_amdgcn_perm(v1, v0, LC.bsel), b23 = __builtin_amdgcn_perm(v3, v2, LC.bsel);
+        const uint32_t pw = i4p_pack_row(b01, b23);
+#else
         const uint32_t q01 = __builtin_amdgcn_perm(v1, v0, LC.psel), q32 = __builtin_amdgcn_perm(v2, v3, LC.psel);
+#if ZW_I4P_TMV
+        const uint32_t p01 = q01, p32 = q32;
+#else
         const uint32_t p01 = LC.tm ? clamp_pk(add_pk(q01, ap01)) : q01;
         const uint32_t p32 = LC.tm ? clamp_pk(add_pk(q32, ap32)) : q32;
-        const uint32_t sw = *(const uint32_t*)(sYh + (by * 4 + r) * 16 + bx * 4);
+#endif
+#if ZW_I4P_DOT4
+        const uint32_t pw = __builtin_amdgcn_perm(p32, p01, ZW_I4P_PAIRS_TO_ROW);  // (TrueMotion clamps in 16-bit form first)
+#endif
+#endif
+#if ZW_I4P_DOT4
+        pp = __builtin_amdgcn_udot4(pw, pw, pp, false);
+        sp = __builtin_amdgcn_udot4(sw, pw, sp, false);
+#else
         const uint32_t d01 = sub_pk(__builtin_amdgcn_perm(0u, sw, 0x0c010c00u), p01);
         const uint32_t d32 = sub_pk(__builtin_amdgcn_perm(0u, sw, 0x0c020c03u), p32);
         pse = dot2v(d01, d01, pse);
         pse = dot2v(d32, d32, pse);
+#endif
     }
+#if ZW_I4P_DOT4
+    const int key = m < 10 ? (int)i4p_rank_key(pp, sp, m) : 0x7fffffff;
+#else
     const int key = m < 10 ? (pse << 4) | m : 0x7fffffff;
+#endif
     const int rank = rank16(key);
     PH_MARK_L(11, l, 0);
 #if ZW_I4P_INV
@@ -1438,15 +1460,20 @@ DI void i4p_step(const Ctx& CA, const Ctx& CB, const int* sbx, const int* sby, i
     const int q0 = LC.q0, qa = LC.qa;
     uint32_t p01, p32;
     {
-        const uint32_t iw = *(const uint32_t*)&Th->i4qa[mv][4 * q];
+        const uint32_t iw = *(const uint32_t*)&Th->i4qp[mv][4 * q];
         uint32_t v[4];
 #pragma unroll
         for (int j = 0; j < 4; j++)
             v[j] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((iw >> (8 * j)) & 255u), (int)vp);
         const uint32_t q01 = __builtin_amdgcn_perm(v[1], v[0], LC.psel), q32 = __builtin_amdgcn_perm(v[2], v[3], LC.psel);
+#if ZW_I4P_TMV
+        p01 = q01;
+        p32 = q32;
+#else
         const bool tm = mv == 1;
         p01 = tm ? clamp_pk(add_pk(q01, ap01)) : q01;
         p32 = tm ? clamp_pk(add_pk(q32, ap32)) : q32;
+#endif
     }
     const uint32_t s01 = __builtin_amdgcn_perm(0u, swq, 0x0c010c00u);
     const uint32_t s32 = __builtin_amdgcn_perm(0u, swq, 0x0c020c03u);
